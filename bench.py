@@ -19,7 +19,15 @@ and the held cross-shard records are exchanged at every quantum boundary;
 the work is the same at every N ("strong" scaling) and the results are
 bit-identical.
 
-Reported with it: the roofline of the dominant kernel by device time
+A plain run (no --full) sets up, warms up, times the --steps steps, writes
+its outputs if --dump-outputs is given and prints the result line: nothing
+else runs.  --dump-outputs DIR writes what the last timed step computed (the
+access words, the per-tile statistics, cache and NoC counters and the run
+info the caller of gg_coherent_run reads back) as DIR/<name>.npy in float64;
+the trace is generated from fixed seeds, so two builds run with the same
+arguments can be compared output for output.
+
+With --full, reported with it: the roofline of the dominant kernel by device time
 (k_c_walk: the X and Y walks are one kernel symbol) at SURVEY.md §8d's 16
 algorithmic bytes per access (8 B address + 4 B meta in, 4 B result out),
 accesses per launch from the run, the average launch duration measured live
@@ -120,6 +128,12 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=3)
     p.add_argument("--warmup", type=int, default=1)
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline: its bit-exact check against the oracle, the CPU baselines, the "
+                        "per-kernel roofline run and the extra sections (the options below that skip or size "
+                        "them apply with --full only)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the outputs of the last timed step as DIR/<name>.npy (float64)")
     p.add_argument("--tiles", type=int, default=1024, help="headline tiles (configs[3]: 1024)")
     p.add_argument("--per-tile", type=int, default=256, help="headline accesses per tile")
     p.add_argument("--hot-lines", type=int, default=256, help="shared hot lines (configs[3]: 256)")
@@ -153,7 +167,10 @@ def parse():
     p.add_argument("--fft-m", type=int, default=20,
                    help="configs[0] section: the reference's FFT -p16 -m<m> (configs[0]: m=20; the trace build() "
                         "captures; m=14 is committed)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps needs at least 1 timed step and --warmup 0 or more")
+    return args
 
 
 def maybe_spawn(args):
@@ -195,12 +212,32 @@ def cpu_share():
     return max(1, min(int(env), aff) if env and env.isdigit() else aff)
 
 
+DUMP_BUDGET_BYTES = 64 << 20   # --dump-outputs: every file together stays below this
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array as path/<name>.npy in float64 (the outputs
+    are u64 words and counters: exact below 2^53, warned about above).  An
+    array past its share of the budget is cut to a fixed, seeded sample of its
+    elements, in index order."""
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_BUDGET_BYTES // (8 * len(arrays)) - 16           # elements per file (16: the .npy header)
+    for name, x in arrays.items():
+        x = np.ascontiguousarray(x)
+        if x.size > cap:
+            x = x.reshape(-1)[np.sort(np.random.default_rng(0).choice(x.size, cap, replace=False))]
+        if x.size and int(x.max()) >= 1 << 53:
+            print("bench.py: --dump-outputs: %s holds values past 2^53, rounded in float64" % name, file=sys.stderr)
+        np.save(os.path.join(path, name + ".npy"), x.astype(np.float64))
+
+
 def coherent_run(args, T, N, H, K, net, world, rank, dev, steps, warmup, verify, cpu, workload="hotspot", l2_assoc=8,
-                 kernel_profile=True):
+                 kernel_profile=True, dump=None):
     """One measurement of Mode C: `warmup` untimed + `steps` timed whole runs,
     barrier + synchronize around the timed region, max over ranks; then (if
     kernel_profile) one untimed run with HIP events around every launch for
-    the per-kernel averages."""
+    the per-kernel averages.  dump: the directory the outputs of the last
+    timed run go to (dump_outputs), or None."""
     import torch
     from graphite_amd import config as C
     from graphite_amd import backend as B
@@ -232,6 +269,7 @@ def coherent_run(args, T, N, H, K, net, world, rank, dev, steps, warmup, verify,
     elapsed = D.max_over_ranks(time.perf_counter() - t0)
     st, cc, ri = be.coherent_stats()
     nc = be.noc_counters()
+    last = out.clone() if dump else None          # the profile run below writes `out` again
     kern = {}
     if kernel_profile:
         # HIP event pairs on the launch stream around every 16th launch of each
@@ -263,13 +301,16 @@ def coherent_run(args, T, N, H, K, net, world, rank, dev, steps, warmup, verify,
            "messages": int(ri[C.RUN_INFO.index("net_msgs")] + ri[C.RUN_INFO.index("self_msgs")]),
            "boundary_records": int(ri[C.RUN_INFO.index("boundary_msgs")]),
            "simulated_ns": int(st[:, 0].max()) // 1000, "kernels": kern}
-    if world > 1:
-        # every rank holds its own tiles' outputs: the node's totals for the check
+    if world > 1 and (verify or dump):
+        # every rank holds its own tiles' outputs: the node's totals for the check and the dump
         import torch.distributed as dist
         tot = [torch.from_numpy(x.view(np.int64).copy()).to(dev) for x in (st, cc, nc)]
-        for x in tot + [out]:
+        for x in tot + [out] + ([last] if dump else []):
             dist.all_reduce(x)
         st, cc, nc = [x.cpu().numpy().view(np.uint64).reshape(y.shape) for x, y in zip(tot, (st, cc, nc))]
+    if rank == 0 and dump:
+        dump_outputs(dump, {"access_words": last.cpu().numpy().view(np.uint64), "tile_stats": st,
+                            "cache_counters": cc, "noc_counters": nc, "run_info": ri})
     if rank == 0 and verify:
         from oracle import pyoracle as po
         a = addr.cpu().numpy().view(np.uint64)
@@ -946,9 +987,12 @@ def main():
     T, N, H, K = args.tiles, args.per_tile, args.hot_lines, args.shards
     if K % world:
         raise SystemExit("bench.py: %d logical shards do not split over %d ranks" % (K, world))
+    # a plain run times the headline and nothing else: the oracle check, the CPU
+    # baseline and the instrumented run for the roofline belong to --full
     head = coherent_run(args, T, N, H, K, net, world, rank, dev, args.steps, args.warmup,
-                        not args.no_verify, world == 1 and not args.no_cpu_baseline,
-                        kernel_profile=not args.no_kernel_profile)
+                        args.full and not args.no_verify,
+                        args.full and world == 1 and not args.no_cpu_baseline,
+                        kernel_profile=args.full and not args.no_kernel_profile, dump=args.dump_outputs)
     if rank == 0:
         kern = {k: v for k, v in head["kernels"].items() if not k.startswith("_")}
         dom = max(kern, key=lambda k: kern[k]["total_ms"]) if kern else None
@@ -978,35 +1022,42 @@ def main():
                        "mode": "coherent", "network": args.net,
                        "parallelism": "%d logical shards over %d rank(s); held cross-shard records exchanged once "
                                       "per quantum%s" % (K, world, " (gg_coherent_run_ranks, RCCL)" if world > 1 else "")},
-            "roofline": {"bound": "hbm", "kernel": KERNEL_SYMBOL.get(dom, dom), "achieved": achieved,
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
-                         "traffic": None, "bytes_per_access": COH_BYTES_PER_ACCESS, "launch_accesses": lacc,
-                         "kernel_avg_us": dk["avg_us"] if dk else None, "kernel_launches": dk["launches"] if dk else None,
-                         "kernels": kern,
-                         "timing": "HIP event pairs on the launch stream around every 16th launch of each "
-                                   "kernel, one extra run; the timed runs carry no instrumentation",
-                         "note": "Mode C is latency-bound: a step is a chain of dependent accesses per tile and each "
-                                 "router port serves its packets one by one in the canonical order (DESIGN.md §4); "
-                                 "the fraction measures how far that is from the HBM bound, not an HBM bottleneck"},
             "coherent": {k: head[k] for k in ("quanta", "steps", "messages", "boundary_records", "simulated_ns",
                                               "seconds_per_run")},
-            "bit_exact_checked": head.get("bit_exact_checked"),
+            "full": args.full,
         }
-        prof = pmc_traffic(KERNEL_SYMBOL.get(dom, dom), "coherent_%s_%dx%d_k%d" % (args.net, T, N, K))
-        if prof:
-            out["roofline"]["traffic"] = prof["bytes"]
-            out["roofline"]["traffic_source"] = prof["source"]
-            if "factors" in prof:
-                out["roofline"]["traffic_factors"] = prof["factors"]
-            out["roofline"]["traffic_note"] = ("HBM bytes per launch (FETCH_SIZE / WRITE_SIZE, calibrated at 8-B loads / "
-                                               "scattered 4-B stores): router queue images and packet records read and "
-                                               "written back per launch, the state SURVEY.md §8d excludes from the "
-                                               "algorithmic bytes")
-        if "cpu_baseline" in head:
-            out["cpu_baseline"] = head["cpu_baseline"]
-    # N > 1: the naturally sharding Mode P leg (private_section, weak scaling,
-    # no data-path collective) beside the coherent headline
+        if args.full:
+            out["bit_exact_checked"] = head.get("bit_exact_checked")
+            out["roofline"] = {"bound": "hbm", "kernel": KERNEL_SYMBOL.get(dom, dom), "achieved": achieved,
+                               "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
+                               "traffic": None, "bytes_per_access": COH_BYTES_PER_ACCESS, "launch_accesses": lacc,
+                               "kernel_avg_us": dk["avg_us"] if dk else None,
+                               "kernel_launches": dk["launches"] if dk else None, "kernels": kern,
+                               "timing": "HIP event pairs on the launch stream around every 16th launch of each "
+                                         "kernel, one extra run; the timed runs carry no instrumentation",
+                               "note": "Mode C is latency-bound: a step is a chain of dependent accesses per tile and "
+                                       "each router port serves its packets one by one in the canonical order "
+                                       "(DESIGN.md §4); the fraction measures how far that is from the HBM bound, "
+                                       "not an HBM bottleneck"}
+            prof = pmc_traffic(KERNEL_SYMBOL.get(dom, dom), "coherent_%s_%dx%d_k%d" % (args.net, T, N, K))
+            if prof:
+                out["roofline"]["traffic"] = prof["bytes"]
+                out["roofline"]["traffic_source"] = prof["source"]
+                if "factors" in prof:
+                    out["roofline"]["traffic_factors"] = prof["factors"]
+                out["roofline"]["traffic_note"] = (
+                    "HBM bytes per launch (FETCH_SIZE / WRITE_SIZE, calibrated at 8-B loads / "
+                    "scattered 4-B stores): router queue images and packet records read and "
+                    "written back per launch, the state SURVEY.md §8d excludes from the "
+                    "algorithmic bytes")
+            if "cpu_baseline" in head:
+                out["cpu_baseline"] = head["cpu_baseline"]
+    # --full, N > 1: the naturally sharding Mode P leg (private_section, weak
+    # scaling, no data-path collective) beside the coherent headline
     secs = [x for x in args.sections.split(",") if x] if world == 1 else ["private"]
+    if not args.full:
+        secs = []
     t_sec = time.perf_counter()
     for name in secs:
         print("bench.py: section %s (%.0f s)" % (name, time.perf_counter() - t_sec), file=sys.stderr, flush=True)

@@ -6,7 +6,7 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 OUT="$GRAFT_REPO_ROOT/gpurun_out/pmc/${PMC_NAME:-run}"
 mkdir -p "$OUT"
-ARGS=${PMC_ARGS:---steps 1 --warmup 0 --no-cpu-baseline --no-verify}
+ARGS=${PMC_ARGS:---full --steps 1 --warmup 0 --no-cpu-baseline --no-verify}
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 120 rocprofv3 -L > "$OUT/../counters_list.txt" 2>&1 || exit $?
 pass() {

@@ -7,7 +7,7 @@ cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 OUT=gpurun_out/r03/${TAG:-noc}
 mkdir -p $OUT
-ARGS="--sections noc --per-tile 16 --steps 1 --warmup 0 --no-cpu-baseline --no-kernel-profile $NOC_ARGS"
+ARGS="--full --sections noc --per-tile 16 --steps 1 --warmup 0 --no-cpu-baseline --no-kernel-profile $NOC_ARGS"
 GG_NOC_PROFILE=1 timeout -k 10 300 python -u bench.py $ARGS > $OUT/bench.json 2> $OUT/bench.err \
   || { tail -30 $OUT/bench.err; exit 1; }
 grep "gg_noc" $OUT/bench.err | tail -6

@@ -15,7 +15,7 @@ if [ -n "$TESTS" ]; then
   tail -3 $OUT/tests.log
 fi
 if [ -n "$BENCH" ]; then
-  timeout -k 10 ${BENCH_LIMIT:-600} python -u bench.py $BENCH_ARGS > $OUT/bench.json 2> $OUT/bench.err \
+  timeout -k 10 ${BENCH_LIMIT:-600} python -u bench.py --full $BENCH_ARGS > $OUT/bench.json 2> $OUT/bench.err \
     || { tail -30 $OUT/bench.err; exit 1; }
   python - "$OUT/bench.json" <<'EOF'
 import json, sys

@@ -10,7 +10,7 @@ if [ "${TESTS:-tests/test_gpu_cache.py}" != "none" ]; then
   tail -2 $OUT/pytest.log
 fi
 for v in ${VARIANTS:-1 0}; do
-  GG_STREAM_T16=$v timeout -k 10 300 python -u bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-kernel-profile --sections private,private_16way $BENCH_ARGS > $OUT/bench_t16_$v.json 2> $OUT/bench_t16_$v.err || { tail -20 $OUT/bench_t16_$v.err; exit 1; }
+  GG_STREAM_T16=$v timeout -k 10 300 python -u bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-kernel-profile --sections private,private_16way $BENCH_ARGS > $OUT/bench_t16_$v.json 2> $OUT/bench_t16_$v.err || { tail -20 $OUT/bench_t16_$v.err; exit 1; }
   python - $OUT/bench_t16_$v.json $v <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

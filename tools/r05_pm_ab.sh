@@ -12,7 +12,7 @@ fi
 i=0
 for lib in ${LIBS:-graphite_amd/libgraphite_gpu.so variants/pm0/libgraphite_gpu.so graphite_amd/libgraphite_gpu.so}; do
   i=$((i+1))
-  GG_LIB=$lib timeout -k 10 300 python -u bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-kernel-profile --sections private,private_16way $BENCH_ARGS > $OUT/bench_$i.json 2> $OUT/bench_$i.err || { tail -20 $OUT/bench_$i.err; exit 1; }
+  GG_LIB=$lib timeout -k 10 300 python -u bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-kernel-profile --sections private,private_16way $BENCH_ARGS > $OUT/bench_$i.json 2> $OUT/bench_$i.err || { tail -20 $OUT/bench_$i.err; exit 1; }
   python - $OUT/bench_$i.json $lib <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -11,7 +11,7 @@ if [ "$TESTS" != "none" ]; then
   timeout -k 10 900 python -u -m pytest $TESTS -m gpu -x -q --timeout 300 --timeout-method thread > $OUT/pytest.log 2>&1 || { tail -40 $OUT/pytest.log; exit 1; }
   tail -2 $OUT/pytest.log
 fi
-timeout -k 10 600 python -u bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-kernel-profile --sections "$SECTIONS" $BENCH_ARGS > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
+timeout -k 10 600 python -u bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-kernel-profile --sections "$SECTIONS" $BENCH_ARGS > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
 python - "$OUT/bench.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -10,7 +10,7 @@ tail -2 $OUT/pytest.log
 for rep in 1 2 3; do
 for v in base ${VARIANTS:-}; do
   if [ $v = base ]; then l=""; else l=$v; fi
-  GG_LIB=$l timeout -k 10 300 python -u bench.py --sections iocoom --steps 1 --warmup 0 --no-cpu-baseline --no-kernel-profile > $OUT/b.json 2> $OUT/b.err || { tail -5 $OUT/b.err; exit 1; }
+  GG_LIB=$l timeout -k 10 300 python -u bench.py --full --sections iocoom --steps 1 --warmup 0 --no-cpu-baseline --no-kernel-profile > $OUT/b.json 2> $OUT/b.err || { tail -5 $OUT/b.err; exit 1; }
   python3 - $OUT/b.json $v <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -5,7 +5,7 @@ OUT=gpurun_out/r06/abs; mkdir -p $OUT
 for rep in 1 2; do
 for v in base variants/ilp2/libgraphite_gpu.so; do
   if [ $v = base ]; then l=""; else l=$v; fi
-  GG_LIB=$l timeout -k 10 400 python -u bench.py --sections iocoom,private,noc,hop_counter,stress,fft --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-profile > $OUT/b.json 2> $OUT/b.err || { tail -5 $OUT/b.err; exit 1; }
+  GG_LIB=$l timeout -k 10 400 python -u bench.py --full --sections iocoom,private,noc,hop_counter,stress,fft --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-profile > $OUT/b.json 2> $OUT/b.err || { tail -5 $OUT/b.err; exit 1; }
   python3 - $OUT/b.json $v <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

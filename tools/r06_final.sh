@@ -13,7 +13,7 @@ if [ -z "$SKIP_TESTS" ]; then
   timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('SMOKE_OK')" > $OUT/smoke.log 2>&1 || { tail -20 $OUT/smoke.log; exit 1; }
   tail -1 $OUT/smoke.log
 fi
-timeout -k 10 1000 python -u bench.py > $OUT/bench_full_sections.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
+timeout -k 10 1000 python -u bench.py --full > $OUT/bench_full_sections.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
 python3 -c "
 import json; d=json.loads(open('$OUT/bench_full_sections.json').read().strip().splitlines()[-1])
 print(d['value'], d['ms_per_step'], d['roofline']['kernel'], d['roofline']['frac'])

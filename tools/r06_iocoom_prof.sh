@@ -8,7 +8,7 @@ set -o pipefail
 cd "$GRAFT_REPO_ROOT" || exit 1
 OUT="$GRAFT_REPO_ROOT/gpurun_out/r06/iocoom"
 mkdir -p "$OUT"
-ARGS="--sections iocoom --steps 1 --warmup 0 --no-cpu-baseline --no-verify --no-kernel-profile"
+ARGS="--full --sections iocoom --steps 1 --warmup 0 --no-cpu-baseline --no-verify --no-kernel-profile"
 ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run --output-format csv -- \
     python3 "$GRAFT_REPO_ROOT/bench.py" $ARGS > "$OUT/trace.log" 2>&1 ) || { tail -5 "$OUT/trace.log"; exit 1; }
 find "$OUT/trace" -name "*kernel_stats.csv" -exec cp {} "$OUT/kernel_stats.csv" \;

@@ -6,7 +6,7 @@ set -o pipefail
 cd "$GRAFT_REPO_ROOT" || exit 1
 OUT=${OUT:-gpurun_out/r06/sect}
 mkdir -p $OUT
-timeout -k 10 600 python -u bench.py --no-cpu-baseline --sections "${SECTIONS-fft,hop_counter,stress}" $BENCH_ARGS \
+timeout -k 10 600 python -u bench.py --full --no-cpu-baseline --sections "${SECTIONS-fft,hop_counter,stress}" $BENCH_ARGS \
   > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
 python3 -c "
 import json; d=json.loads(open('$OUT/bench.json').read().strip().splitlines()[-1])
