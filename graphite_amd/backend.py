@@ -321,7 +321,9 @@ class Backend:
     def coherent_run_ranks(self, comm_ptr, addr, meta, tile_offsets, out=None, stream=None):
         """The whole coherent run over the ranks of an RCCL communicator
         (gg_coherent_run_ranks; comm_ptr = ncclComm_t as an int, e.g.
-        ProcessGroupNCCL._comm_ptr()).  This context owns the rank's shards."""
+        ProcessGroupNCCL._comm_ptr()).  This context owns the rank's shards.
+        The trace may hold BARRIER records: the round releases them as
+        coherent_run does, bit-identical for any split over ranks."""
         import torch
         if out is not None:
             _need_dev(out, torch.int64, addr.numel())
@@ -338,7 +340,10 @@ class Backend:
 
     def round_pack(self, world, rank, q):
         """gg_round_pack: quantum q's steps + the tail on the context's stream;
-        returns the RoundIO with the device slots / words to move."""
+        returns the RoundIO with the device slots / words to move.  The
+        ROUND_WORDS status words are opaque to the transport (they carry the
+        rank's barrier waiters too: round_unpack's commit releases a barrier
+        every unfinished tile of every rank has reached)."""
         io = RoundIO()
         _check(load().gg_round_pack(self.h, world, rank, q, ctypes.byref(io)))
         return io

@@ -48,7 +48,9 @@ def next_quantum(q, quantum_ps, msgs, active, blocked, min_next_ps):
 
 
 def run(engine, quantum_ps, num_shards, world=1, rank=0, backend=None, device="cpu"):
-    """Run every quantum.  Returns the number of quanta executed."""
+    """Run every quantum.  Returns the number of quanta executed.  Traces
+    with BARRIER records are not for this driver (the engine's quantum()
+    rejects them): use run_rccl."""
     import torch
     if world > 1:
         import torch.distributed as dist
@@ -139,5 +141,8 @@ def run_rccl(backend, addr, meta, tile_offsets, out=None, group=None, stream=Non
     """The whole coherent run of this rank's shards with the exchange in the C
     ABI (gg_coherent_run_ranks: gg_round_exchange over the group's RCCL
     communicator at every quantum boundary) - the same rounds as `run`,
-    without a host round trip per collective."""
+    without a host round trip per collective.  Unlike `run` (whose engine
+    surface, gg_coherent_quantum, rejects them) it takes traces with BARRIER
+    records: the round releases a barrier once every unfinished tile of
+    every rank waits at one."""
     backend.coherent_run_ranks(rccl_comm_ptr(group), addr, meta, tile_offsets, out, stream)

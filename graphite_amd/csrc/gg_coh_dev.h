@@ -137,6 +137,8 @@ struct Seg { uint32_t line, lo, hi, pad; };       // a run of row (X) / column (
 // next start, quanta completed, quantum length
 enum { QS_Q = 0, QS_START, QS_DONE, QS_ARRIVED, QS_ACTIVE, QS_BLOCKED, QS_MIN_NEXT, QS_COUNT, QS_QPS,
        QS_BWAIT, QS_BMAX, QS_REL, QS_N };   // barrier waits, their latest arrival, release (max + 1, or 0)
+// QS_REL is also written by the multi-rank round (k_c_round_commit, from the
+// ranks' gathered status words) for step 0 of its next host-indexed quantum
 constexpr uint32_t kBarWait = 2;          // Tile::blocked of a tile waiting at a BARRIER record
 // gap cycles before a record (a BARRIER record is taken at the tile's clock)
 __device__ __forceinline__ uint64_t rec_gap(uint32_t meta)
@@ -2721,16 +2723,18 @@ __device__ __forceinline__ void quantum_end(const CP& P, const CS& S, uint32_t L
 
 // devloop: the quantum, its barrier and the step index come from S.qs (the
 // quantum loop runs on the device, gg_coherent_run); otherwise the host
-// drives one quantum (gg_coherent_quantum) and L is the step index.
+// drives one quantum (gg_coherent_quantum, the multi-rank round) and L is the
+// step index; its step 0 takes the barrier release the round's commit stored.
 // the tile's trace window: records wbase + lane (kept across the steps of a
 // persistent launch; the records are read-only for the whole run)
 struct TraceWin { uint64_t wbase, wa; uint32_t wm; };
 constexpr uint64_t kNsFin = ~0ull, kNsBlk = ~0ull - 1;   // next start of a finished / blocked tile
+constexpr uint64_t kRelRead = ~0ull;     // tile_step's release argument: read S.qs[QS_REL] (no release time + 1 is ~0)
 
 template <bool LC, bool HR, bool F, int PR, class SL, class H>
 __device__ __forceinline__ uint64_t tile_step(const CP& P, const CS& S, uint32_t lt, uint32_t k, uint32_t L, uint64_t barrier,
                                           TraceWin& W, SL& sl, uint8_t* clds, const TilePre& pre, const H& hk,
-                                          uint32_t na, uint32_t ni, uint64_t rel);
+                                          uint32_t na, uint32_t ni, uint64_t rel_in, bool rel_host);
 
 // LC: cache state in LDS; HR: L1 hit runs (persistent small meshes, where
 // long runs of hits between misses pay for the window look-up)
@@ -2784,8 +2788,17 @@ __device__ __forceinline__ void step_body(const CP& P, const CS& S, uint32_t L, 
   const GHooks hk{P, S};
   const uint32_t na = P.net == GG_NET_EMESH_HOP_BY_HOP ? (p ? pre.narv1 : pre.narv0) : 0u;
   const uint32_t ni = p ? pre.ninb1 : pre.ninb0;
-  tile_step<LC, HR, F, PR>(P, S, lt, k, L, barrier, W, sl, smem + P.cache_lds_off, pre, hk, na, ni,
-                    devloop && k == 0 ? qsv[QS_REL] : 0ull);
+  // the barrier release for step 0: the device-driven loop hands it over from
+  // the lanes above; a host-indexed step 0 (the multi-rank round) has tile_step
+  // read what k_c_round_commit stored — told by a flag, or in the MOSI instance
+  // by the value kRelRead (the form in which that instance's SGPR spills do
+  // not grow: tools/resource_usage.py)
+  if constexpr (PR == 1)
+    tile_step<LC, HR, F, PR>(P, S, lt, k, L, barrier, W, sl, smem + P.cache_lds_off, pre, hk, na, ni,
+                      k == 0 ? (devloop ? qsv[QS_REL] : kRelRead) : 0ull, false);
+  else
+    tile_step<LC, HR, F, PR>(P, S, lt, k, L, barrier, W, sl, smem + P.cache_lds_off, pre, hk, na, ni,
+                      devloop && k == 0 ? qsv[QS_REL] : 0ull, !devloop && k == 0);
 }
 
 // Publish of a hop-by-hop step whose sent records all fit the LDS sent list
@@ -2928,7 +2941,7 @@ __device__ __forceinline__ void publish_hbh_lds(TT& T, gg_cmsg* cur, uint32_t nl
 template <bool LC, bool HR, bool F, int PR, class SL, class H>
 __device__ __forceinline__ uint64_t tile_step(const CP& P, const CS& S, uint32_t lt, uint32_t k, uint32_t L, uint64_t barrier,
                                           TraceWin& W, SL& sl, uint8_t* clds, const TilePre& pre, const H& hk,
-                                          uint32_t na, uint32_t ni, uint64_t rel)
+                                          uint32_t na, uint32_t ni, uint64_t rel_in, bool rel_host)
 {
   const uint32_t ln = lane_id(), p = k & 1u;
   PROF_T0();
@@ -3199,6 +3212,11 @@ __device__ __forceinline__ uint64_t tile_step(const CP& P, const CS& S, uint32_t
   }
 
   PROF_AT(_p2);
+  // the release word: the device-driven loop hands it over from the lanes of
+  // its quantum state; a host-indexed step 0 (the multi-rank round) reads what
+  // k_c_round_commit stored, here and not at the step's start, where the value
+  // would be live across the message phase (SGPR spills of every instance)
+  const uint64_t rel = (PR == 1 ? rel_in == kRelRead : rel_host) ? S.qs[QS_REL] : rel_in;
   // a barrier released at the quantum boundary: continue at the latest
   // arrival (the SyncInstruction of sync_client.cc:308-314 is the stall)
   if (rel && T.blocked == kBarWait) {

@@ -18,7 +18,7 @@ __global__ void k_c_import(CP P, CS S, const gg_cmsg* in, uint32_t n)
   import_one(P, S, in[i], &S.imp[0]);
 }
 
-// any BARRIER record in the trace (only gg_coherent_run releases barriers)
+// any BARRIER record in the trace (gg_coherent_quantum has no release: its caller picks the next quantum)
 __global__ void k_has_barrier(const uint32_t* meta, uint64_t n, uint32_t* flag)
 {
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
@@ -102,29 +102,31 @@ __global__ void k_c_ri_quantum(CS S, uint64_t q)
   S.ri[GG_RI_FINAL_QUANTUM] = q;
 }
 // ---- one round of gg_round_exchange with one host sync (see there) --------
-// words of a rank's round status (gathered over the ranks, reduced by each)
-enum { RW_SENT = 0, RW_ACTIVE, RW_BLOCKED, RW_ERR, RW_MAXSLOT, RW_MINNEXT, RW_NOTDONE, RW_STEPS, RW_N };
-static_assert(RW_N == kRoundWords, "gg_internal.h kRoundWords");
+// words of a rank's round status (gathered over the ranks, reduced by each): RW_* in gg_internal.h
 // before RCCL: if the quantum's steps have finished (quiet), the status of the
-// owned tiles and the held records scattered into the send slots by owning
-// rank; else empty slots and the not-done word.  Nothing here changes the
-// context's state: a round another rank has not finished is repeated.
+// owned tiles (quantum_end's: the tiles waiting at a BARRIER record apart from
+// the tiles blocked on a miss, and out of the least next start) and the held
+// records scattered into the send slots by owning rank; else empty slots and
+// the not-done flag.  Nothing here changes the context's state: a round
+// another rank has not finished is repeated.
 __global__ void __launch_bounds__(1024) k_c_round_tail(CP P, CS S, gg_cmsg* slots, uint32_t world, uint32_t per_rank,
                                                       uint64_t region, const uint32_t* err, uint32_t host_err,
                                                       uint64_t* dv)
 {
-  __shared__ unsigned long long st[3];                 // active, blocked, least next start
+  __shared__ unsigned long long st[5];                 // active, blocked, least next start, barrier waiters, their latest clock
   const uint32_t tid = threadIdx.x, nt = blockDim.x;
   const uint32_t quiet = *(volatile uint32_t*)S.quiet;
   for (uint32_t r = tid; r < world; r += nt) slots[(size_t)r * (region + 1)].addr = 0;
-  if (tid < 3) st[tid] = tid == 2 ? ~0ull : 0ull;
+  if (tid < 5) st[tid] = tid == 2 ? ~0ull : 0ull;
   __syncthreads();
   if (quiet) {
-    for (uint32_t lt = tid; lt < P.L; lt += nt) {      // k_c_status
+    for (uint32_t lt = tid; lt < P.L; lt += nt) {      // k_c_status, with quantum_end's barrier words
       const uint64_t r = S.ts[lt].rec;
       if (r >= S.ts[lt].rec_end) continue;
       atomicAdd(&st[0], 1ull);
-      if (S.ts[lt].blocked) { atomicAdd(&st[1], 1ull); continue; }
+      const uint32_t b = S.ts[lt].blocked;
+      if (b == kBarWait) { atomicAdd(&st[3], 1ull); atomicMax(&st[4], (unsigned long long)S.ts[lt].clk); continue; }
+      if (b) { atomicAdd(&st[1], 1ull); continue; }
       atomicMin(&st[2], (unsigned long long)(S.ts[lt].clk + rec_gap(S.meta[r]) * P.gap_ps));
     }
     const uint32_t n = *(volatile uint32_t*)S.bnd_cnt;
@@ -145,22 +147,35 @@ __global__ void __launch_bounds__(1024) k_c_round_tail(CP P, CS S, gg_cmsg* slot
     sent += c; mx = c > mx ? c : mx;
   }
   dv[RW_SENT] = sent; dv[RW_ACTIVE] = st[0]; dv[RW_BLOCKED] = st[1];
-  dv[RW_ERR] = (uint64_t)(__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) | host_err);
+  dv[RW_FLAGS] = (uint64_t)(__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) | host_err) |
+                 (quiet ? (uint64_t)(quiet - 1) << kRwStepsShift : kRwNotDone);
   dv[RW_MAXSLOT] = mx; dv[RW_MINNEXT] = st[2];
-  dv[RW_NOTDONE] = quiet ? 0ull : 1ull; dv[RW_STEPS] = quiet ? quiet - 1 : 0ull;
+  dv[RW_BWAIT] = st[3]; dv[RW_BMAX] = st[4];
 }
 __device__ __forceinline__ bool round_go(const uint64_t* dv_all, uint32_t world)
 {
   uint64_t bad = 0;
-  for (uint32_t r = 0; r < world; ++r) bad |= dv_all[(size_t)r * RW_N + RW_ERR] | dv_all[(size_t)r * RW_N + RW_NOTDONE];
+  for (uint32_t r = 0; r < world; ++r) bad |= dv_all[(size_t)r * RW_N + RW_FLAGS] & (kRwErrMask | kRwNotDone);
   return bad == 0;
 }
 // after RCCL, when every rank finished its quantum with no error: the
 // quantum's end on this rank (step counters, held list, run info, record
-// pools for the import)
+// pools for the import) and the barrier release, quantum_end's rule over the
+// gathered words of every rank (so every rank stores the same value): with
+// nothing in flight, no tile blocked on a miss and every unfinished tile at a
+// BARRIER record, all continue at the latest arrival — step 0 of the next
+// quantum takes S.qs[QS_REL] = that clock + 1; 0 releases nobody.  Rewritten
+// at every commit; a repeated round commits nothing and continues past step 0.
 __global__ void k_c_round_commit(CP P, CS S, uint64_t q, const uint64_t* dv_all, uint32_t world)
 {
   if (threadIdx.x != 0 || !round_go(dv_all, world)) return;
+  uint64_t msgs = 0, active = 0, blocked = 0, bwait = 0, bmax = 0;
+  for (uint32_t r = 0; r < world; ++r) {
+    const uint64_t* w = dv_all + (size_t)r * RW_N;
+    msgs += w[RW_SENT]; active += w[RW_ACTIVE]; blocked += w[RW_BLOCKED]; bwait += w[RW_BWAIT];
+    bmax = w[RW_BMAX] > bmax ? w[RW_BMAX] : bmax;
+  }
+  S.qs[QS_REL] = (msgs == 0 && blocked == 0 && bwait == active && active != 0) ? bmax + 1 : 0ull;
   for (int i = 0; i < 7; ++i) S.ring[i] = 0;           // ring[4], quiet, imp[2]
   *S.bnd_cnt = 0;
   S.ri[GG_RI_QUANTA]++;
@@ -220,7 +235,7 @@ struct gg_coh_state {
   bool persist_lc = false;
   bool begun = false;
   uint64_t gen = 0;                     // gg_coherent_begin count: a round in progress belongs to one run
-  bool has_barrier = false;             // the bound trace holds BARRIER records (gg_coherent_run only)
+  bool has_barrier = false;             // the bound trace holds BARRIER records (not for gg_coherent_quantum)
   uint32_t* bar_flag = nullptr;
   // live kernel timing (gg_set_timing): an event pair around every
   // kTimeSample-th launch of each kernel (mode 1; a pair around every launch,
@@ -730,7 +745,8 @@ static gg_status coh_quantum_steps(gg_ctx* ctx, uint64_t q)
 {
   gg_coh_state* C = ctx->coh;
   if (C->has_barrier)
-    return gg_fail(GG_ERR_UNSUPPORTED, "BARRIER records are released by gg_coherent_run only (one context)");
+    return gg_fail(GG_ERR_UNSUPPORTED, "BARRIER records are released by gg_coherent_run and the round "
+                                       "(gg_round_*, gg_coherent_run_ranks), not quantum by quantum");
   hipStream_t s = ctx->last_stream;
   const CP& P = C->P;
   const uint64_t quantum_ps = (uint64_t)ctx->cfg.quantum_ns * 1000ull;
@@ -798,8 +814,6 @@ gg_status gg_coh_steps_async(gg_ctx* ctx, uint64_t q, uint32_t k0, uint32_t n)
 {
   gg_coh_state* C = ctx->coh;
   if (!C || !C->begun) return gg_fail(GG_ERR_INVALID, "gg_coherent_begin first");
-  if (C->has_barrier)
-    return gg_fail(GG_ERR_UNSUPPORTED, "BARRIER records are released by gg_coherent_run only (one context)");
   hipSetDevice(ctx->device);
   hipStream_t s = ctx->last_stream;
   const CP& P = C->P;

@@ -160,7 +160,23 @@ gg_status gg_coh_round_tail(gg_ctx* ctx, gg_cmsg* slots, uint32_t world, uint32_
 gg_status gg_coh_round_import(gg_ctx* ctx, uint64_t q, const gg_cmsg* send, const gg_cmsg* recv, uint32_t world,
                               uint32_t self, uint64_t region, uint64_t slot, const uint64_t* dv_all, uint64_t* counts);
 void      gg_coh_harvest(gg_ctx* ctx);
-constexpr int kRoundWords = 8;          // a rank's round status words (RW_* in gg_coherent.hip)
+// A rank's round status words (written by k_c_round_tail, gathered over the
+// ranks, reduced by k_c_round_commit on the device and by round_decide on the
+// host; internal: the transport moves them as GG_ROUND_WORDS opaque words).
+//   RW_SENT     records held for other shards at the quantum's end (all slots)
+//   RW_ACTIVE   owned tiles with an unfinished trace
+//   RW_BLOCKED  of those, blocked on a miss (not at a BARRIER record)
+//   RW_FLAGS    bits 0..31 the rank's error flags (GG_DERR_*), bit 32 not-done
+//               (the step batch ended before the quantum), bits 33.. the steps
+//               the quantum took
+//   RW_MAXSLOT  the largest record count of one send slot
+//   RW_MINNEXT  least next start (ps) of the tiles neither blocked nor waiting
+//   RW_BWAIT    of the active tiles, waiting at a BARRIER record
+//   RW_BMAX     their latest arrival: max clock (ps, 64 bits), 0 with no waiter
+enum { RW_SENT = 0, RW_ACTIVE, RW_BLOCKED, RW_FLAGS, RW_MAXSLOT, RW_MINNEXT, RW_BWAIT, RW_BMAX, RW_N };
+constexpr int kRoundWords = RW_N;
+constexpr uint64_t kRwErrMask = 0xFFFFFFFFull, kRwNotDone = 1ull << 32;
+constexpr int kRwStepsShift = 33;
 gg_status gg_coh_import_slots(gg_ctx* ctx, const gg_cmsg* slots, uint32_t world, uint64_t region, uint64_t lo,
                               uint64_t hi, bool first, const uint64_t* skip_if_dev);
 gg_status gg_coh_check(gg_ctx* ctx);

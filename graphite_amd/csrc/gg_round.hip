@@ -18,6 +18,13 @@
 // the round runs again with more steps.  Only a quantum whose records
 // overflow a slot takes a second, sized round.
 //
+// BARRIER records (SimBarrier, sync_server.cc:133-170) are released by the
+// round as by gg_coherent_run's quantum_end: the words carry each rank's
+// waiters and their latest arrival, the commit kernel of every rank reduces
+// the gathered words to the same release time and step 0 of the next quantum
+// applies it — on the device, inside the enqueued round; round_decide only
+// mirrors the rule to pick the next quantum.
+//
 // Failure is decided collectively: a rank whose quantum or export failed still
 // posts every send / receive and the all-gather (with its error flag in its
 // status words), the commit and imports are skipped on the device when any
@@ -194,7 +201,7 @@ gg_status round_pack(gg_ctx* ctx, uint32_t W, uint32_t R, uint64_t q, gg_round_i
     // the tail did not run: the words say so (best effort), the transport still runs
     if (!B->herr) { B->herr = GG_DERR_STATE; B->est = st; B->emsg = gg_last_error(); }
     std::vector<uint64_t> w(kRoundWords, 0);
-    w[3] = GG_DERR_STATE;
+    w[RW_FLAGS] = GG_DERR_STATE;                       // an error flag, no waiter, no release
     hipMemcpyAsync(B->dv, w.data(), sizeof(uint64_t) * kRoundWords, hipMemcpyHostToDevice, ctx->last_stream);
     for (uint32_t r = 0; r < W; ++r)
       hipMemsetAsync(B->send + (size_t)r * (region + 1), 0, sizeof(gg_cmsg), ctx->last_stream);
@@ -204,15 +211,25 @@ gg_status round_pack(gg_ctx* ctx, uint32_t W, uint32_t R, uint64_t q, gg_round_i
   return GG_OK;
 }
 
-// the quantum's end after every slot is in: the reduced words decide
+// the quantum's end after every slot is in: the reduced words decide, by
+// quantum_end's rule (gg_coh_dev.h) with its held-record count = msgs:
+//   nothing active, nothing in flight                          the run is over
+//   nothing in flight, a tile blocked on a miss                deadlock (waiters or not)
+//   nothing in flight, every active tile at a BARRIER record   release: k_c_round_commit stored the latest
+//                                                              arrival + 1 for step 0 of the next quantum
+//   nothing in flight otherwise                                skip to the least next start (some tile
+//                                                              neither blocked nor waiting has one: the
+//                                                              waiters stay until the others arrive or finish)
+//   records in flight                                          the next quantum
 gg_status round_decide(gg_ctx* ctx, RoundBufs* B, gg_round_io* io)
 {
   const uint64_t* h = B->host;
   const int W = B->world;
-  uint64_t msgs = 0, active = 0, blocked = 0, mn = ~0ull;
+  uint64_t msgs = 0, active = 0, blocked = 0, bwait = 0, mn = ~0ull;
   for (int r = 0; r < W; ++r) {
     const uint64_t* w = h + (size_t)r * kRoundWords;
-    msgs += w[0]; active += w[1]; blocked += w[2]; mn = std::min(mn, w[5]);
+    msgs += w[RW_SENT]; active += w[RW_ACTIVE]; blocked += w[RW_BLOCKED]; bwait += w[RW_BWAIT];
+    mn = std::min(mn, w[RW_MINNEXT]);
   }
   const uint64_t q = B->q;
   const uint64_t qps = (uint64_t)ctx->cfg.quantum_ns * 1000ull;
@@ -225,6 +242,18 @@ gg_status round_decide(gg_ctx* ctx, RoundBufs* B, gg_round_io* io)
     return gg_coh_check(ctx);
   }
   if (msgs == 0 && blocked != 0) return gg_fail(GG_ERR_STATE, "coherent run deadlocked: tiles blocked with no message in flight");
+  if (msgs == 0 && bwait == active) {
+    // a release: a waiter stopped at a clock before this quantum's lax barrier
+    // (clk < (q + 1) * quantum), so the latest arrival / quantum <= q and
+    // quantum_end's max(q + 1, latest / quantum) is q + 1
+    io->next_q = q + 1;
+    return GG_OK;
+  }
+  // waiters nobody can join: active = waiters + tiles with a next start here
+  // (blocked == 0), so this cannot happen unless the words are inconsistent
+  if (msgs == 0 && mn == ~0ull)
+    return gg_fail(GG_ERR_STATE, "coherent run deadlocked: %llu of %llu unfinished tiles wait at a barrier and no "
+                                 "other tile can run", (unsigned long long)bwait, (unsigned long long)active);
   io->next_q = (msgs == 0) ? std::max<uint64_t>(q + 1, mn / qps) : q + 1;
   return GG_OK;
 }
@@ -264,7 +293,8 @@ gg_status gg_round_unpack(gg_ctx* ctx, gg_round_io* io)
   const uint64_t* h = B->host;
   uint64_t err = 0, notdone = 0, mx = 0;
   for (int r = 0; r < W; ++r) {
-    err |= h[r * kRoundWords + 3]; notdone |= h[r * kRoundWords + 6]; mx = std::max(mx, h[r * kRoundWords + 4]);
+    const uint64_t* w = h + (size_t)r * kRoundWords;
+    err |= w[RW_FLAGS] & kRwErrMask; notdone |= w[RW_FLAGS] & kRwNotDone; mx = std::max(mx, w[RW_MAXSLOT]);
   }
   if (err) {
     io->state = GG_ROUND_DONE;
@@ -277,7 +307,7 @@ gg_status gg_round_unpack(gg_ctx* ctx, gg_round_io* io)
   // (they hold clean words), the next round carries it to every rank
   if (lerr) set_pending(B, lerr, lmsg);
   if (notdone) { B->again = true; io->state = GG_ROUND_AGAIN; return GG_OK; }   // some rank's quantum is still running
-  B->steps_hist[B->hist_i++ & 3] = (uint32_t)std::max<uint64_t>(1, h[(size_t)B->rank * kRoundWords + 7]);
+  B->steps_hist[B->hist_i++ & 3] = (uint32_t)std::max<uint64_t>(1, h[(size_t)B->rank * kRoundWords + RW_FLAGS] >> kRwStepsShift);
   if (mx > B->slot) {
     // a slot overflowed somewhere: every rank takes the sized round (the
     // counts are known on both sides now); the own slot's tail is a local copy

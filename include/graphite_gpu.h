@@ -102,14 +102,20 @@ enum { GG_LOC_INVALID = 0, GG_LOC_L1I = 2, GG_LOC_L1D = 3 };
  * barrier (SimBarrier::wait, sync_server.cc:133-170 with the count = those
  * tiles), then all continue at the latest arrival time (SyncServer::
  * barrierWait replies max_time, :357-383; the MCP is a system tile, so the
- * messages cost no network time).  gg_coherent_run applies the release at the
- * quantum boundary after the last arrival and writes the record's access
- * word as (stall_ps << 2) | GG_LVL_SYNC.  Only gg_coherent_run takes traces
- * with barriers (the per-quantum and multi-rank entry points return
- * GG_ERR_UNSUPPORTED; the private-cache batch flags one in the device error
- * word, so the next gg_cache_get_counters returns GG_ERR_UNSUPPORTED;
- * gg_split_accesses rejects one in its access trace: insert barriers into
- * the line records it writes).  Barriers carry no id or count: one global
+ * messages cost no network time).  The release is applied at the quantum
+ * boundary after the last arrival and the record's access word written as
+ * (stall_ps << 2) | GG_LVL_SYNC.  Traces with barriers are taken by
+ * gg_coherent_run (one context) and by the multi-rank round: gg_round_pack /
+ * _unpack / _finish, gg_round_exchange, gg_coherent_run_ranks — the ranks'
+ * status words carry their waiters and latest arrival, and every rank
+ * releases alike, bit-identical to one context.  They are not taken by
+ * gg_coherent_quantum / _export / _import (gg_coherent_quantum returns
+ * GG_ERR_UNSUPPORTED: its caller picks the next quantum from a
+ * gg_coherent_status that has no barrier fields) nor by the private-cache
+ * batch (it flags one in the device error word, so the next
+ * gg_cache_get_counters returns GG_ERR_UNSUPPORTED); gg_split_accesses
+ * rejects one in its access trace: insert barriers into the line records it
+ * writes.  Barriers carry no id or count: one global
  * barrier whose count is "every tile with an unfinished trace", released at
  * the quantum boundary after its last arrival.                 */
 #define GG_META_BARRIER 0xFFFFFFFFu
@@ -506,7 +512,13 @@ gg_status gg_coherent_run(gg_ctx* ctx, const gg_trace* trace, uint64_t* access_o
  * the ranks' status words and imports the records, with one host sync (a
  * rank whose step batch was short repeats the round); *next_q is the quantum
  * every rank runs next and *done 1 when the run is over (GG_ERR_STATE on a
- * deadlock).  It replaces the reference's per-message transport
+ * deadlock).  BARRIER records are released by the round: when the gathered
+ * words show nothing in flight, no tile blocked on a miss and every
+ * unfinished tile of every rank waiting at a barrier, each rank's commit
+ * kernel stores the latest arrival and step 0 of quantum q + 1 continues the
+ * waiters there (no further host sync; *next_q = q + 1).  While only some
+ * tiles wait, the others run on; tiles that finish leave the count.
+ * It replaces the reference's per-message transport
  * (common/transport/socktransport.cc) plus its lax barrier round
  * (lax_barrier_sync_client.cc:31-69, lax_barrier_sync_server.cc:57-160).
  * gg_coherent_run_ranks = gg_coherent_begin + rounds from quantum 0 until done. */
@@ -529,8 +541,13 @@ gg_status gg_coherent_run_ranks(gg_ctx* ctx, void* nccl_comm, const gg_trace* tr
  *   transport 1: once the context's stream has finished the pack, for every
  *     r != rank: records [0, 1 + slot) of send + r * stride into rank r's
  *     recv + rank * stride; and words_own into words_all + rank *
- *     GG_ROUND_WORDS of every rank (this rank's too: an all-gather).
- *   gg_round_unpack: commit + import on the stream, the gathered words to the
+ *     GG_ROUND_WORDS of every rank (this rank's too: an all-gather).  The
+ *     words are opaque to the transport (their layout is internal: records
+ *     sent, active / blocked tiles, flags + steps, largest slot, least next
+ *     start, barrier waiters, their latest arrival).
+ *   gg_round_unpack: commit (with the barrier release for the next quantum's
+ *     step 0, decided from every rank's words) + import on the stream, the
+ *     gathered words to the
  *     host, one sync; io->state = GG_ROUND_AGAIN (some rank's quantum had not
  *     finished: pack again with the same q), GG_ROUND_OVERFLOW (a slot held
  *     more than `slot` records: send_count[r] / recv_count[r] records are in
