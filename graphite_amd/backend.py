@@ -24,9 +24,10 @@ _ERR = {-1: "GG_ERR_INVALID", -2: "GG_ERR_HIP", -3: "GG_ERR_UNSUPPORTED", -4: "G
 
 
 class GGError(RuntimeError):
-    def __init__(self, code, msg):
+    def __init__(self, code, msg, statuses=None):
         super().__init__("%s: %s" % (_ERR.get(code, code), msg))
         self.code = code
+        self.statuses = statuses     # coherent_run_many: the status of every instance
 
 
 class LineInfo(ctypes.Structure):
@@ -60,7 +61,9 @@ EXPORTS = ["gg_abi_version", "gg_last_error", "gg_config_default", "gg_create", 
            "gg_kernel_stats", "gg_round_exchange", "gg_coherent_run_ranks", "gg_gen_stress_trace",
            "gg_split_accesses", "gg_combine_accesses", "gg_dump_summary", "gg_core_model_run", "gg_core_get_stats", "gg_coherent_get_miss_types",
            "gg_coherent_get_protocol_stats", "gg_iocoom_run", "gg_iocoom_get_stats",
-           "gg_round_pack", "gg_round_unpack", "gg_round_finish"]
+           "gg_round_pack", "gg_round_unpack", "gg_round_finish", "gg_coherent_run_many"]
+
+MANY_MAX = 4096          # GG_MANY_MAX
 
 
 class RoundIO(ctypes.Structure):
@@ -140,12 +143,15 @@ def load():
     L.gg_round_pack.argtypes = [vp, u32, u32, u64, ctypes.POINTER(RoundIO)]
     L.gg_round_unpack.argtypes = [vp, ctypes.POINTER(RoundIO)]
     L.gg_round_finish.argtypes = [vp, ctypes.POINTER(RoundIO)]
+    L.gg_coherent_run_many.argtypes = [ctypes.POINTER(vp), u32, ctypes.POINTER(_Trace), ctypes.POINTER(vp),
+                                       ctypes.POINTER(i32), vp]
     for name in ["gg_kernel_stats", "gg_shard_map", "gg_coherent_begin", "gg_coherent_quantum", "gg_coherent_export",
                  "gg_coherent_import", "gg_coherent_run", "gg_coherent_get_stats", "gg_gen_hotspot_trace",
                  "gg_round_exchange", "gg_coherent_run_ranks", "gg_gen_stress_trace", "gg_split_accesses",
                  "gg_combine_accesses", "gg_dump_summary", "gg_core_model_run", "gg_core_get_stats",
                  "gg_coherent_get_miss_types", "gg_coherent_get_protocol_stats", "gg_iocoom_run",
-                 "gg_iocoom_get_stats", "gg_round_pack", "gg_round_unpack", "gg_round_finish"]:
+                 "gg_iocoom_get_stats", "gg_round_pack", "gg_round_unpack", "gg_round_finish",
+                 "gg_coherent_run_many"]:
         getattr(L, name).restype = i32
     for name in ["gg_reset", "gg_cache_access_batch", "gg_cache_get_counters", "gg_cache_get_line_info",
                  "gg_cache_set_line_info", "gg_cache_access_line", "gg_cache_insert_line",
@@ -467,6 +473,37 @@ class Backend:
                                            p.ctypes.data_as(ctypes.c_void_p), t.size,
                                            d.ctypes.data_as(ctypes.c_void_p)))
         return d
+
+
+def coherent_run_many(backends, addrs, metas, tile_offsets, outs=None, stream=None):
+    """An ensemble of independent coherent runs in one set of launches
+    (gg_coherent_run_many): backends[i] runs the trace addrs[i] / metas[i] /
+    tile_offsets[i] into outs[i] (outs, or an entry, may be None).  The
+    backends must be launch-compatible (include/graphite_gpu.h).  Returns the
+    list of per-instance statuses; if any is non-zero raises GGError carrying
+    that list (e.statuses) — the other instances have run to their end."""
+    import torch
+    n = len(backends)
+    if not (len(addrs) == len(metas) == len(tile_offsets) == n) or (outs is not None and len(outs) != n):
+        raise ValueError("one trace (and one output, if any) per backend")
+    traces = (_Trace * max(n, 1))()
+    keep = []                                       # the host offset arrays, alive for the call
+    for i, be in enumerate(backends):
+        if outs is not None and outs[i] is not None:
+            _need_dev(outs[i], torch.int64, addrs[i].numel())
+        traces[i] = be._trace(addrs[i], metas[i], tile_offsets[i])
+        keep.append(be._keep)
+    hs = (ctypes.c_void_p * max(n, 1))(*[be.h for be in backends])
+    op = None
+    if outs is not None:
+        op = (ctypes.c_void_p * max(n, 1))(*[o.data_ptr() if o is not None else None for o in outs])
+    st = (ctypes.c_int * max(n, 1))()
+    rc = load().gg_coherent_run_many(hs, n, traces, op, st, _stream(stream))
+    del keep
+    statuses = [int(st[i]) for i in range(n)]
+    if rc != GG_OK:
+        raise GGError(rc, load().gg_last_error().decode(errors="replace"), statuses)
+    return statuses
 
 
 def shard_map(num_tiles, num_shards):

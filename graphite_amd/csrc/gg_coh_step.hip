@@ -3,7 +3,7 @@
 // (gg_coh_step_fast.hip) when the configuration allows it (P.fast), and
 // k_c_step<false, 1> (gg_coh_step_mosi.hip) for the MOSI protocol and
 // k_c_step<false, 2> (gg_coh_step_shl2.hip) for the shared-L2 MSI protocol.
-#include "gg_coh_dev.h"
+#include "gg_coh_many.h"
 
 namespace ggc {
 
@@ -23,6 +23,7 @@ hipError_t step_set_lds(size_t step_lds, size_t persist_lc_lds, size_t persist_l
   if (e == hipSuccess) e = step_mosi_set_lds(step_lds);
   if (e == hipSuccess) e = step_shl2_set_lds(step_lds);
   if (e == hipSuccess) e = persist_set_lds(persist_lc_lds, persist_lds);
+  if (e == hipSuccess) e = step_many_set_lds(step_lds);          // the ensemble twins (gg_coh_many_step*.hip)
   return e;
 }
 

@@ -1,7 +1,7 @@
 // gg_coh_walk.hip — the hop-by-hop walker kernels k_c_walk<PIPE, RQ> (one
 // workgroup per X / Y run) and their host launcher.  Device
 // code: gg_coh_dev.h.
-#include "gg_coh_dev.h"
+#include "gg_coh_many.h"
 
 namespace ggc {
 
@@ -35,7 +35,7 @@ hipError_t walk_set_lds(size_t lds)
   for (const void* f : {(const void*)k_c_walk<true, true>, (const void*)k_c_walk<true, false>,
                         (const void*)k_c_walk<false, true>, (const void*)k_c_walk<false, false>})
     if (hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
-  return hipSuccess;
+  return walk_many_set_lds(lds);                     // the ensemble twins (gg_coh_many_walk.hip)
 }
 
 }  // namespace ggc

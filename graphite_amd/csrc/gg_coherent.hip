@@ -2,7 +2,7 @@
 // small kernels (reset, import / export, the round) and the host side of
 // gg_coherent_* / the round.  Device code and the design notes: gg_coh_dev.h;
 // the step and walker kernels: gg_coh_step.hip, gg_coh_walk.hip.
-#include "gg_coh_dev.h"
+#include "gg_coh_many.h"
 
 #include <algorithm>
 #include <cmath>
@@ -212,6 +212,19 @@ __global__ void k_c_import_slots(CP P, CS S, const gg_cmsg* slots, uint64_t regi
     import_one(P, S, sl[1 + i], &S.imp[0]);
 }
 
+// gg_coherent_run_many's look at a batch: the run-over word and the error
+// words of every live instance into one buffer (one copy, one sync)
+__global__ void k_many_poll(const ManyPair* __restrict__ pairs, uint32_t live, ManyPoll* __restrict__ out)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= live) return;
+  const CS* S = pairs[i].S;
+  const uint32_t* err = S->err;
+  out[i].done = S->qs[QS_DONE];
+  out[i].err = err[0];
+  out[i].err_line = err[1];
+}
+
 }  // namespace ggc
 
 using namespace ggc;
@@ -236,6 +249,11 @@ struct gg_coh_state {
   bool begun = false;
   uint64_t gen = 0;                     // gg_coherent_begin count: a round in progress belongs to one run
   bool has_barrier = false;             // the bound trace holds BARRIER records (not for gg_coherent_quantum)
+  // gg_coherent_run_many with this context first: the live pairs and the poll
+  // words, device and pinned host ([cap] ManyPair then [cap] ManyPoll each)
+  void* many_dev = nullptr;
+  void* many_host = nullptr;
+  uint32_t many_cap = 0;
   uint32_t* bar_flag = nullptr;
   // live kernel timing (gg_set_timing): an event pair around every
   // kTimeSample-th launch of each kernel (mode 1; a pair around every launch,
@@ -371,6 +389,8 @@ void gg_coh_free(gg_ctx* ctx)
   if (!C) return;
   for (hipEvent_t e : C->tev) hipEventDestroy(e);
   for (void* p : C->allocs) hipFree(p);
+  if (C->many_dev) hipFree(C->many_dev);
+  if (C->many_host) hipHostFree(C->many_host);
   delete C;
   ctx->coh = nullptr;
 }
@@ -1058,6 +1078,148 @@ gg_status gg_coherent_run(gg_ctx* ctx, const gg_trace* tr, uint64_t* access_out_
   GG_HIP(hipMemcpy(&done, C->S.qs + QS_DONE, sizeof(done), hipMemcpyDeviceToHost));
   if (done == 2) return gg_fail(GG_ERR_STATE, "coherent run deadlocked: tiles blocked with no message in flight");
   return GG_OK;
+}
+
+// ---- gg_coherent_run_many: independent runs side by side in one set of
+// launches.  What fixes the shape of an ensemble launch —
+// grids, block sizes, kernel variants — must be the same in every context;
+// it is read from the derived launch state, so any two configs that derive
+// the same shape go together.  Returns the first field that differs.
+static const char* many_mismatch(const gg_ctx* a, const gg_ctx* b)
+{
+  const gg_coh_state *A = a->coh, *B = b->coh;
+  const CP &p = A->P, &q = B->P;
+  if (a->device != b->device) return "device";
+  if (p.T != q.T) return "num_tiles";
+  if (p.K != q.K) return "num_shards";
+  if (p.mosi != q.mosi || p.shl2 != q.shl2 || p.mesi != q.mesi) return "protocol";
+  if (p.net != q.net) return "net_model";
+  if (p.L != q.L) return "owned tiles";
+  if (p.fast != q.fast) return "step kernel variant (register queues and no miss types, or the general form)";
+  if (p.nsx != q.nsx || p.nsy != q.nsy) return "walker run counts";
+  if (p.nsx + p.nsy && walk_regq(p) != walk_regq(q)) return "walker kernel variant (register queues)";
+  if (p.nsx + p.nsy && (A->wtx != B->wtx || A->wty != B->wty)) return "walker block sizes";
+  return nullptr;
+}
+
+gg_status gg_coherent_run_many(gg_ctx* const* ctxs, uint32_t n, const gg_trace* traces, uint64_t* const* access_out_dev,
+                               gg_status* statuses, void* stream)
+{
+  // every rejection comes before a launch or a change of any context's run state
+  if (n == 0) return gg_fail(GG_ERR_INVALID, "gg_coherent_run_many: n == 0");
+  if (n > GG_MANY_MAX) return gg_fail(GG_ERR_INVALID, "gg_coherent_run_many: n = %u above GG_MANY_MAX = %u", n, (unsigned)GG_MANY_MAX);
+  if (!ctxs || !traces) return gg_fail(GG_ERR_INVALID, "gg_coherent_run_many: NULL argument");
+  {
+    std::vector<std::pair<const gg_ctx*, uint32_t>> seen(n);
+    for (uint32_t i = 0; i < n; ++i) {
+      if (!ctxs[i]) return gg_fail(GG_ERR_INVALID, "gg_coherent_run_many: context %u is NULL", i);
+      seen[i] = {ctxs[i], i};
+    }
+    std::sort(seen.begin(), seen.end());
+    uint32_t dup = ~0u, of = 0;
+    for (uint32_t i = 1; i < n; ++i)
+      if (seen[i].first == seen[i - 1].first && seen[i].second < dup) { dup = seen[i].second; of = seen[i - 1].second; }
+    if (dup != ~0u) return gg_fail(GG_ERR_INVALID, "gg_coherent_run_many: context %u is context %u again", dup, of);
+  }
+  for (uint32_t i = 0; i < n; ++i) {
+    const gg_config& c = ctxs[i]->cfg;
+    const uint32_t K = c.num_shards ? c.num_shards : 1;
+    if (c.shard_begin != 0 || (c.shard_end != 0 && c.shard_end != K))
+      return gg_fail(GG_ERR_INVALID, "gg_coherent_run_many: context %u does not own every shard (shard range [%u, %u) of %u)",
+                     i, c.shard_begin, c.shard_end, K);
+  }
+  // the derived launch state of a context that has not run yet (allocation
+  // only, as gg_coherent_begin's first call: nothing is reset or launched)
+  for (uint32_t i = 0; i < n; ++i) {
+    hipSetDevice(ctxs[i]->device);
+    if (gg_status st = coh_alloc(ctxs[i])) return st;
+  }
+  for (uint32_t i = 1; i < n; ++i)
+    if (const char* f = many_mismatch(ctxs[0], ctxs[i]))
+      return gg_fail(GG_ERR_INVALID, "gg_coherent_run_many: context %u differs from context 0 in %s", i, f);
+
+  gg_ctx* c0 = ctxs[0];
+  gg_coh_state* C0 = c0->coh;
+  hipSetDevice(c0->device);
+  hipStream_t s = (hipStream_t)stream;
+  if (C0->many_cap < n) {
+    if (C0->many_dev) hipFree(C0->many_dev);
+    if (C0->many_host) hipHostFree(C0->many_host);
+    C0->many_dev = C0->many_host = nullptr; C0->many_cap = 0;
+    const size_t bytes = (size_t)n * (sizeof(ManyPair) + sizeof(ManyPoll));
+    GG_HIP(hipMalloc(&C0->many_dev, bytes));
+    GG_HIP(hipHostMalloc(&C0->many_host, bytes, hipHostMallocDefault));
+    C0->many_cap = n;
+  }
+  ManyPair* pairs_d = (ManyPair*)C0->many_dev;
+  ManyPoll* poll_d = (ManyPoll*)(pairs_d + C0->many_cap);
+  ManyPair* pairs_h = (ManyPair*)C0->many_host;
+  ManyPoll* poll_h = (ManyPoll*)(pairs_h + C0->many_cap);
+
+  std::vector<gg_status> stv(n, GG_OK);
+  std::vector<uint64_t> done(n, 0);
+  std::vector<uint32_t> err(n, 0), live;
+  size_t walk_lds = 0, step_lds = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    stv[i] = gg_coherent_begin(ctxs[i], &traces[i], access_out_dev ? access_out_dev[i] : nullptr, stream);
+    if (stv[i] == GG_OK) live.push_back(i);
+    walk_lds = std::max(walk_lds, ctxs[i]->coh->walk_lds);
+    step_lds = std::max(step_lds, ctxs[i]->coh->step_lds);
+  }
+  const CP& P = C0->P;                              // the shared launch shape
+  const bool hbh = P.net == GG_NET_EMESH_HOP_BY_HOP;
+  // every instance lays its LDS out from its own CP inside its own size: the
+  // launch takes the largest (the sizes need not match)
+  gg_status hip_st = GG_OK;
+  auto hip = [&](hipError_t e, const char* what) { if (e != hipSuccess && hip_st == GG_OK) hip_st = gg_hip_check(e, what); return e == hipSuccess; };
+  if (!live.empty()) {
+    hip(step_many_set_lds(step_lds), "hipFuncSetAttribute(k_c_step_many)");
+    if (hbh) hip(walk_many_set_lds(walk_lds), "hipFuncSetAttribute(k_c_walk_many)");
+  }
+  gg_timer_begin(c0, "coherent_run", s);
+  // per-step launches only: the persistent kernel's grid barrier needs every
+  // workgroup of every instance resident at once (no ensemble form).  After
+  // each batch the instances that finished or failed leave the live list.
+  uint32_t L = 0, batch = 16;
+  while (!live.empty() && hip_st == GG_OK) {
+    const uint32_t m = (uint32_t)live.size();
+    for (uint32_t j = 0; j < m; ++j) pairs_h[j] = ManyPair{ctxs[live[j]]->coh->Pd, ctxs[live[j]]->coh->Sd};
+    if (!hip(hipMemcpyAsync(pairs_d, pairs_h, sizeof(ManyPair) * m, hipMemcpyHostToDevice, s), "hipMemcpyAsync(live list)")) break;
+    for (uint32_t b = 0; b < batch; ++b, ++L) {
+      launch_step_many(P, pairs_d, m, step_lds, s, L);
+      if (hbh) {
+        if (P.nsx) launch_walk_many(C0->wtx > 64, walk_regq(P), P.nsx, C0->wtx, pairs_d, m, walk_lds, s, L, 0);
+        if (P.nsy) launch_walk_many(C0->wty > 64, walk_regq(P), P.nsy, C0->wty, pairs_d, m, walk_lds, s, L, 1);
+      }
+    }
+    hipLaunchKernelGGL(k_many_poll, dim3((m + 63) / 64), dim3(64), 0, s, (const ManyPair*)pairs_d, m, poll_d);
+    if (!hip(hipGetLastError(), "ensemble launches")) break;
+    if (!hip(hipMemcpyAsync(poll_h, poll_d, sizeof(ManyPoll) * m, hipMemcpyDeviceToHost, s), "hipMemcpyAsync(poll)")) break;
+    if (!hip(hipStreamSynchronize(s), "hipStreamSynchronize")) break;
+    std::vector<uint32_t> next;
+    for (uint32_t j = 0; j < m; ++j) {
+      const uint32_t i = live[j];
+      done[i] = poll_h[j].done; err[i] = poll_h[j].err;
+      if (!err[i] && !done[i]) next.push_back(i);
+    }
+    live.swap(next);
+    if (batch < 256) batch *= 2;
+  }
+  gg_timer_end(c0, "coherent_run", s);
+  if (hip_st == GG_OK) hip(hipStreamSynchronize(s), "hipStreamSynchronize");
+  for (uint32_t i : live) stv[i] = hip_st;            // (only a HIP failure leaves instances live)
+  for (uint32_t i = 0; i < n; ++i) {
+    if (stv[i] != GG_OK) continue;
+    if (err[i]) stv[i] = coh_check(ctxs[i]);
+    else if (done[i] == 2)
+      stv[i] = gg_fail(GG_ERR_STATE, "coherent run deadlocked: tiles blocked with no message in flight (instance %u)", i);
+  }
+  gg_status first = GG_OK;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (statuses) statuses[i] = stv[i];
+    if (first == GG_OK) first = stv[i];
+  }
+  return first;
 }
 
 gg_status gg_coherent_get_miss_types(gg_ctx* ctx, uint64_t* out)

@@ -503,6 +503,48 @@ gg_status gg_coherent_quantum(gg_ctx* ctx, uint64_t q, gg_coherent_status* st);
 gg_status gg_coherent_export(gg_ctx* ctx, gg_cmsg* out_dev, uint64_t cap, uint64_t* per_shard_counts);
 gg_status gg_coherent_import(gg_ctx* ctx, const gg_cmsg* in_dev, uint64_t n);
 gg_status gg_coherent_run(gg_ctx* ctx, const gg_trace* trace, uint64_t* access_out_dev, void* stream);
+/* An ensemble: n independent coherent runs side by side in one set of
+ * launches (a sweep over traces or over latency / cache-timing settings; a
+ * 16- or 64-tile run alone leaves most of the card empty).  ctxs[i] is an
+ * ordinary context of gg_create that owns every shard, traces[i] its trace,
+ * access_out_dev[i] its output buffer (an entry, or the array, may be NULL).
+ * Each instance does what gg_coherent_run does, bit for bit, and afterwards
+ * every per-context getter (gg_coherent_get_stats, _get_miss_types,
+ * _get_protocol_stats, gg_noc_get_counters, gg_dump_summary,
+ * gg_core_model_run) works on each context as after a single run.
+ * statuses[i] (may be NULL) receives instance i's status; the return value is
+ * the first non-zero one, or GG_OK.  A device error in one instance (a
+ * capacity, a deadlock) fails that instance alone, with gg_coherent_run's
+ * status; the others run to their end.  Instances that finish or fail leave
+ * the launches at the next batch boundary, so short runs do not pay for long
+ * ones.
+ * Launch-compatible contexts.  The contexts must derive the same launch
+ * shape: device; num_tiles, num_shards, protocol and network model; the step
+ * kernel variant (register-held history-tree queues with no miss-type
+ * tracking, or the general form; MOSI; shared L2) and, under
+ * emesh_hop_by_hop, the walker variant (pipeline or sweep, register queues
+ * or not) with its block sizes and run counts.  The rule is applied to the
+ * derived launch state, not to config fields: whatever leaves that state
+ * alike may differ — the trace and its length (BARRIER records included),
+ * frequency_ghz, every *_cycles latency, dram_latency_ns, dram_bandwidth,
+ * router_delay, link_delay, quantum_ns, miss_track_lines, and max_list_size
+ * as long as the queue form stays the same.  Dynamic LDS sizes need not
+ * match: each instance lays out its own, the launch takes the largest.
+ * GG_ERR_INVALID, with gg_last_error naming the first offending index and
+ * field, for: n == 0, n > GG_MANY_MAX, a NULL context, a context listed
+ * twice, a context that does not own every shard, an incompatible context
+ * (compared with context 0).  These are found before any launch or any
+ * change to a context's run state (a context that has never run gets its
+ * coherent state allocated for the comparison, nothing more).
+ * The persistent small-mesh kernel is never used here: its grid barrier
+ * needs every workgroup of every instance resident at once, and a mistake
+ * there hangs the device.  The per-step launches give bit-identical results
+ * (gg_coherent_run has both forms).  Launches are not timed per kernel; the
+ * "coherent_run" timer of gg_set_timing covers the whole call on ctxs[0].
+ * One stream, one host thread; synchronous.                                 */
+#define GG_MANY_MAX 4096u
+gg_status gg_coherent_run_many(gg_ctx* const* ctxs, uint32_t n, const gg_trace* traces,
+                               uint64_t* const* access_out_dev, gg_status* statuses, void* stream);
 /* The coherent mode over ranks (one process per GPU), RCCL over xGMI.
  * nccl_comm is an ncclComm_t (RCCL) of W ranks; rank r's context must own
  * logical shards [r*K/W, (r+1)*K/W) (cfg.shard_begin / shard_end, K =
