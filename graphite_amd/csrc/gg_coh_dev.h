@@ -2670,28 +2670,35 @@ __device__ __forceinline__ uint32_t xy_stage_seg(const CP& P, const CS& S, uint3
 
 __device__ __forceinline__ void import_one(const CP& P, const CS& S, const gg_cmsg& m, uint32_t* resumed);
 
-// The end of a quantum in the device-driven loop (the launch after the step
-// that sent nothing): every tile adds its status, the blocks deliver the held
-// boundary records into the next quantum, and the last block to arrive picks
-// the next quantum as gg_coherent_run / oracle_coh_run do (empty quanta
-// skipped; blocked tiles with nothing in flight = deadlock).
+// The end of a quantum in the device-driven loop (hop-by-hop: in the walker
+// launch of the step that sent nothing, quantum_end_walk; otherwise in the
+// step launch after it, quantum_end): every tile adds its status, the blocks
+// deliver the held boundary records into the next quantum, and the last block
+// to arrive picks the next quantum as gg_coherent_run / oracle_coh_run do
+// (empty quanta skipped; blocked tiles with nothing in flight = deadlock).
+
+// one owned tile's status into the quantum state
+__device__ __forceinline__ void qend_tile(const CP& P, const CS& S, uint32_t lt)
+{
+  const uint64_t r = S.ts[lt].rec;
+  if (r < S.ts[lt].rec_end) {
+    atomicAdd((unsigned long long*)&S.qs[QS_ACTIVE], 1ull);
+    const uint32_t b = S.ts[lt].blocked;
+    if (b == kBarWait) {
+      atomicAdd((unsigned long long*)&S.qs[QS_BWAIT], 1ull);
+      atomicMax((unsigned long long*)&S.qs[QS_BMAX], (unsigned long long)S.ts[lt].clk);
+    } else if (b) atomicAdd((unsigned long long*)&S.qs[QS_BLOCKED], 1ull);
+    else atomicMin((unsigned long long*)&S.qs[QS_MIN_NEXT],
+                   (unsigned long long)(S.ts[lt].clk + rec_gap(S.meta[r]) * P.gap_ps));
+  }
+}
+__device__ __forceinline__ void qend_pick(const CS& S, uint32_t L, uint64_t q, uint64_t Q, uint32_t nb);
+
+// k_c_step's form: one workgroup (one wave) per owned tile
 __device__ __forceinline__ void quantum_end(const CP& P, const CS& S, uint32_t L, uint64_t q, uint64_t Q)
 {
   const uint32_t ln = threadIdx.x, lt = blockIdx.x;
-  volatile uint64_t* qs = S.qs;
-  if (ln == 0) {
-    const uint64_t r = S.ts[lt].rec;
-    if (r < S.ts[lt].rec_end) {
-      atomicAdd((unsigned long long*)&S.qs[QS_ACTIVE], 1ull);
-      const uint32_t b = S.ts[lt].blocked;
-      if (b == kBarWait) {
-        atomicAdd((unsigned long long*)&S.qs[QS_BWAIT], 1ull);
-        atomicMax((unsigned long long*)&S.qs[QS_BMAX], (unsigned long long)S.ts[lt].clk);
-      } else if (b) atomicAdd((unsigned long long*)&S.qs[QS_BLOCKED], 1ull);
-      else atomicMin((unsigned long long*)&S.qs[QS_MIN_NEXT],
-                     (unsigned long long)(S.ts[lt].clk + rec_gap(S.meta[r]) * P.gap_ps));
-    }
-  }
+  if (ln == 0) qend_tile(P, S, lt);
   const uint32_t nb = *(volatile uint32_t*)S.bnd_cnt;
   for (uint32_t i = lt * 64 + ln; i < nb; i += gridDim.x * 64) import_one(P, S, S.bnd[i], &S.imp[(Q + 1) & 1]);
   __syncthreads();
@@ -2699,6 +2706,38 @@ __device__ __forceinline__ void quantum_end(const CP& P, const CS& S, uint32_t L
   __threadfence();
   if (atomicAdd((unsigned long long*)&S.qs[QS_ARRIVED], 1ull) != gridDim.x - 1) return;
   __threadfence();
+  qend_pick(S, L, q, Q, nb);
+}
+
+// The walker launch's form (the launch of slot L whose step sent nothing ends
+// the quantum itself, so no launch is spent on it): the workgroups are runs,
+// not tiles, so the tiles and the held records are spread over every thread
+// of the grid (thread t of block b is b + nblk * t: each block takes a few
+// tiles).  The import fills the run lists and inboxes of the next quantum's
+// step 0; no block of this launch walks (each saw the same "sent nothing"),
+// and the last block to arrive marks slot L dead for a later walker launch of
+// the slot.
+__device__ __forceinline__ void quantum_end_walk(const CP& P, const CS& S, uint32_t L, uint64_t q, uint64_t Q, uint32_t blk,
+                                                 uint32_t nblk)
+{
+  const uint32_t tid = threadIdx.x, g = blk + nblk * tid, gn = nblk * blockDim.x;
+  for (uint32_t lt = g; lt < P.L; lt += gn) qend_tile(P, S, lt);
+  const uint32_t nb = *(volatile uint32_t*)S.bnd_cnt;
+  for (uint32_t i = g; i < min(nb, P.msg_cap); i += gn)      // (a count past the pool was flagged GG_DERR_CAP at the put)
+    import_one(P, S, S.bnd[i], &S.imp[(Q + 1) & 1]);
+  __syncthreads();
+  if (tid != 0) return;
+  __threadfence();
+  if (atomicAdd((unsigned long long*)&S.qs[QS_ARRIVED], 1ull) != nblk - 1) return;
+  __threadfence();
+  S.live[L & 3] = 0;
+  qend_pick(S, L, q, Q, nb);
+}
+
+// the last workgroup to arrive: the next quantum, and the quantum state reset
+__device__ __forceinline__ void qend_pick(const CS& S, uint32_t L, uint64_t q, uint64_t Q, uint32_t nb)
+{
+  volatile uint64_t* qs = S.qs;
   const uint64_t active = qs[QS_ACTIVE], blocked = qs[QS_BLOCKED], mn = qs[QS_MIN_NEXT], qps = qs[QS_QPS];
   const uint64_t bw = qs[QS_BWAIT], bmax = qs[QS_BMAX];
   S.ri[GG_RI_QUANTA]++;
@@ -3618,8 +3657,10 @@ __host__ __device__ inline bool walk_regq(const CP& P)
   return P.np.qm && P.np.qtype == GG_QM_HISTORY_TREE && P.np.max_size <= kQMax;
 }
 
+// qend: the number of workgroups of a launch that also hosts the quantum end
+// (the slot's first walker launch in gg_coherent_run's per-step loop), else 0
 template <bool PIPE, bool RQ>
-__device__ __forceinline__ void walk_body(const CP& P, const CS& S, uint32_t L, int stage, uint32_t blk)
+__device__ __forceinline__ void walk_body(const CP& P, const CS& S, uint32_t L, int stage, uint32_t blk, uint32_t qend = 0)
 {
   // block -> (run slot, direction): with runs interleaved by shard, block b
   // takes slot (b mod ns) + ns * (b div 2ns) in direction (b div ns) & 1, so
@@ -3639,7 +3680,18 @@ __device__ __forceinline__ void walk_body(const CP& P, const CS& S, uint32_t L, 
   const uint32_t n0 = *cntp;
   const Seg sd = (stage == 0 ? S.segx : S.segy)[sg >> 1];
   const uint64_t lw = tid < P.seg_cap ? list[tid] : 0ull;
+  // (the same round: what the step launch of slot L + 1 would have read to
+  // find that this step sent nothing)
+  uint32_t sent = 1;
+  uint64_t qe_q = 0, qe_Q = 0;
+  if (qend) {
+    const uint32_t r0 = S.ring[0], r1 = S.ring[1], r2 = S.ring[2], r3 = S.ring[3], i0 = S.imp[0], i1 = S.imp[1];
+    qe_q = S.qs[QS_Q]; qe_Q = S.qs[QS_COUNT];
+    const uint32_t k = live - 1, km = k & 3;
+    sent = (km == 0 ? r0 : km == 1 ? r1 : km == 2 ? r2 : r3) + (k == 0 ? ((qe_Q & 1) ? i1 : i0) : 0u);
+  }
   if (!live) return;                                 // launch L was no step
+  if (sent == 0) { quantum_end_walk(P, S, L, qe_q, qe_Q, blk, qend); return; }   // the quantum's last step
   const uint32_t p = (live - 1) & 1u;
   PROF_T0();
   if (n0 == 0) return;
@@ -4227,7 +4279,7 @@ void launch_persist_lc(const CP& P, const StepArgs& a, size_t lds, hipStream_t s
 hipError_t persist_lc_set_lds(size_t lds);
 hipError_t persist_lc_occ(size_t lds, int* per_cu);
 void launch_walk(bool pipe, bool rq, uint32_t blocks, uint32_t threads, size_t lds, hipStream_t s, const StepArgs& a,
-                 uint32_t L, int stage);
+                 uint32_t L, int stage, bool qend);
 hipError_t walk_set_lds(size_t lds);
 
 }  // namespace ggc

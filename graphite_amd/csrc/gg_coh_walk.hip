@@ -5,9 +5,11 @@
 
 namespace ggc {
 
+// qend: the launch also ends the quantum when its slot's step sent nothing
+// (quantum_end_walk; the slot's first walker launch in gg_coherent_run's loop)
 template <bool PIPE, bool RQ>
 __global__ void __launch_bounds__(PIPE ? 64 * kMaxWalkWaves : 64) k_c_walk(const CP* __restrict__ Pp, const CS* __restrict__ Sp, uint32_t L, int stage,
-                                                                         unsigned long long* kt, uint32_t kt_slot)
+                                                                         unsigned long long* kt, uint32_t kt_slot, uint32_t qend)
 {
   kwarm(Pp, Sp);
   const CP& P = *Pp;                 // the launch state read on use (see k_c_step)
@@ -15,7 +17,7 @@ __global__ void __launch_bounds__(PIPE ? 64 * kMaxWalkWaves : 64) k_c_walk(const
   if (kt && threadIdx.x == 0) kt[(size_t)kt_slot * S.kt_stride + 2 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
   if (DG(S.trs) && L < S.tr_n && threadIdx.x == 0)
     DG(S.trw)[(((size_t)L * 2 + stage) * S.tr_wb + blockIdx.x) * 8] = __builtin_amdgcn_s_memrealtime();
-  walk_body<PIPE, RQ>(P, S, L, stage, blockIdx.x);
+  walk_body<PIPE, RQ>(P, S, L, stage, blockIdx.x, qend ? gridDim.x : 0u);
   if (kt) {
     __syncthreads();
     if (threadIdx.x == 0) kt[(size_t)kt_slot * S.kt_stride + 2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
@@ -23,12 +25,13 @@ __global__ void __launch_bounds__(PIPE ? 64 * kMaxWalkWaves : 64) k_c_walk(const
 }
 
 void launch_walk(bool pipe, bool rq, uint32_t blocks, uint32_t threads, size_t lds, hipStream_t s, const StepArgs& a,
-                 uint32_t L, int stage)
+                 uint32_t L, int stage, bool qend)
 {
-  if (pipe && rq) hipLaunchKernelGGL((k_c_walk<true, true>), dim3(blocks), dim3(threads), lds, s, a.P, a.S, L, stage, a.kt, a.kt_slot);
-  else if (pipe) hipLaunchKernelGGL((k_c_walk<true, false>), dim3(blocks), dim3(threads), lds, s, a.P, a.S, L, stage, a.kt, a.kt_slot);
-  else if (rq) hipLaunchKernelGGL((k_c_walk<false, true>), dim3(blocks), dim3(64), lds, s, a.P, a.S, L, stage, a.kt, a.kt_slot);
-  else hipLaunchKernelGGL((k_c_walk<false, false>), dim3(blocks), dim3(64), lds, s, a.P, a.S, L, stage, a.kt, a.kt_slot);
+  const uint32_t q = qend ? 1u : 0u;
+  if (pipe && rq) hipLaunchKernelGGL((k_c_walk<true, true>), dim3(blocks), dim3(threads), lds, s, a.P, a.S, L, stage, a.kt, a.kt_slot, q);
+  else if (pipe) hipLaunchKernelGGL((k_c_walk<true, false>), dim3(blocks), dim3(threads), lds, s, a.P, a.S, L, stage, a.kt, a.kt_slot, q);
+  else if (rq) hipLaunchKernelGGL((k_c_walk<false, true>), dim3(blocks), dim3(64), lds, s, a.P, a.S, L, stage, a.kt, a.kt_slot, q);
+  else hipLaunchKernelGGL((k_c_walk<false, false>), dim3(blocks), dim3(64), lds, s, a.P, a.S, L, stage, a.kt, a.kt_slot, q);
 }
 hipError_t walk_set_lds(size_t lds)
 {

@@ -274,9 +274,10 @@ struct gg_coh_state {
 constexpr uint64_t kTimeSample = 16;
 constexpr uint32_t kKtRing = 1024;      // in-kernel timing slots between two harvests (a batch is <= 256 steps)
 static StepArgs step_args(const gg_coh_state* C) { return StepArgs{C->Pd, C->Sd, C->S.kt, C->S.kt_slot}; }
-static void launch_walk(gg_coh_state* C, hipStream_t s, uint32_t blocks, uint32_t threads, uint32_t L, int stage)
+static void launch_walk(gg_coh_state* C, hipStream_t s, uint32_t blocks, uint32_t threads, uint32_t L, int stage,
+                        bool qend = false)
 {
-  ggc::launch_walk(threads > 64, walk_regq(C->P), blocks, threads, C->walk_lds, s, step_args(C), L, stage);
+  ggc::launch_walk(threads > 64, walk_regq(C->P), blocks, threads, C->walk_lds, s, step_args(C), L, stage, qend);
 }
 constexpr uint32_t kPersistTiles = 64;        // owned tiles up to which gg_coherent_run uses k_c_persist
 constexpr uint32_t kPersistLaunches = 16384;  // launch indices per k_c_persist launch
@@ -993,12 +994,18 @@ gg_status gg_coherent_run(gg_ctx* ctx, const gg_trace* tr, uint64_t* access_out_
     timed_harvest(C);
     if (err || done) break;
   }
+  // hop-by-hop: the first walker launch of a slot ends the quantum when the
+  // slot's step sent nothing (quantum_end_walk), so no launch is spent on the
+  // quantum end; GG_COH_QEND_STEP=1 (A/B knob): the step launch after it does,
+  // as for the closed-form networks (k_c_step's quantum_end)
+  const char* qs_env = getenv("GG_COH_QEND_STEP");
+  const bool qend_walk = hbh && !(qs_env && atoi(qs_env));
   for (; !persist;) {
     for (uint32_t b = 0; b < batch; ++b, ++L) {
       timed_launch(ctx, C, s, 0, [&] { launch_step(P, step_args(C), C->step_lds, s, L, 1u, (uint64_t)0); });
       if (hbh) {
-        if (P.nsx) timed_launch(ctx, C, s, 1, [&] { launch_walk(C, s, P.nsx, C->wtx, L, 0); });
-        if (P.nsy) timed_launch(ctx, C, s, 2, [&] { launch_walk(C, s, P.nsy, C->wty, L, 1); });
+        if (P.nsx) timed_launch(ctx, C, s, 1, [&] { launch_walk(C, s, P.nsx, C->wtx, L, 0, qend_walk); });
+        if (P.nsy) timed_launch(ctx, C, s, 2, [&] { launch_walk(C, s, P.nsy, C->wty, L, 1, qend_walk && !P.nsx); });
       }
     }
     GG_HIP(hipGetLastError());
