@@ -61,7 +61,13 @@ EXPORTS = ["gg_abi_version", "gg_last_error", "gg_config_default", "gg_create", 
            "gg_kernel_stats", "gg_round_exchange", "gg_coherent_run_ranks", "gg_gen_stress_trace",
            "gg_split_accesses", "gg_combine_accesses", "gg_dump_summary", "gg_core_model_run", "gg_core_get_stats", "gg_coherent_get_miss_types",
            "gg_coherent_get_protocol_stats", "gg_iocoom_run", "gg_iocoom_get_stats",
-           "gg_round_pack", "gg_round_unpack", "gg_round_finish", "gg_coherent_run_many"]
+           "gg_round_pack", "gg_round_unpack", "gg_round_finish", "gg_coherent_run_many",
+           "gg_stats_trace_configure", "gg_stats_trace_sample", "gg_stats_trace_get", "gg_stats_trace_dump"]
+
+# statistics trace (gg_stats_trace_*): GG_ST_* statistics bits, GG_STF_* sample fields
+ST_NETWORK_UTILIZATION, ST_CACHE_LINE_REPLICATION = 1, 2
+ST_FIELDS = ["time_ns", "repeat", "flits_sent", "flits_broadcasted", "flits_received",
+             "l1_exclusive", "l1_shared", "l2_exclusive", "l2_shared"]
 
 MANY_MAX = 4096          # GG_MANY_MAX
 
@@ -145,6 +151,12 @@ def load():
     L.gg_round_finish.argtypes = [vp, ctypes.POINTER(RoundIO)]
     L.gg_coherent_run_many.argtypes = [ctypes.POINTER(vp), u32, ctypes.POINTER(_Trace), ctypes.POINTER(vp),
                                        ctypes.POINTER(i32), vp]
+    L.gg_stats_trace_configure.argtypes = [vp, u32, u64, u64]
+    L.gg_stats_trace_sample.argtypes = [vp, u64]
+    L.gg_stats_trace_get.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
+    L.gg_stats_trace_dump.argtypes = [vp, i32, ctypes.c_char_p, u64, ctypes.POINTER(u64)]
+    for name in ["gg_stats_trace_configure", "gg_stats_trace_sample", "gg_stats_trace_get", "gg_stats_trace_dump"]:
+        getattr(L, name).restype = i32
     for name in ["gg_kernel_stats", "gg_shard_map", "gg_coherent_begin", "gg_coherent_quantum", "gg_coherent_export",
                  "gg_coherent_import", "gg_coherent_run", "gg_coherent_get_stats", "gg_gen_hotspot_trace",
                  "gg_round_exchange", "gg_coherent_run_ranks", "gg_gen_stress_trace", "gg_split_accesses",
@@ -463,6 +475,47 @@ class Backend:
         _check(L.gg_dump_summary(self.h, fmt, None, 0, ctypes.byref(need)))
         buf = ctypes.create_string_buffer(need.value)
         _check(L.gg_dump_summary(self.h, fmt, buf, need.value, ctypes.byref(need)))
+        return buf.value.decode()
+
+    # ---- statistics trace ([statistics_trace]: gg_stats_trace_*) ----------
+    def stats_trace_configure(self, statistics, sampling_interval_ns=0, max_samples=0):
+        """The trace of the coherent runs begun from now on: statistics = a bit
+        set of ST_NETWORK_UTILIZATION / ST_CACHE_LINE_REPLICATION (0: off), the
+        sampling interval (a multiple of cfg.quantum_ns) and the sample
+        buffer's size (a full buffer fails the run)."""
+        _check(load().gg_stats_trace_configure(self.h, statistics, sampling_interval_ns, max_samples))
+
+    def stats_trace_sample(self, barrier_time_ns):
+        """Append one sample of the context's current state (between
+        host-driven quanta, or after a finished run)."""
+        _check(load().gg_stats_trace_sample(self.h, barrier_time_ns))
+
+    def stats_trace(self):
+        """The samples so far: {field: uint64 [n]} for ST_FIELDS, and
+        "sharer_hist": uint64 [n][num_tiles + 1] (bin k = directory entries
+        with k sharers)."""
+        L = load()
+        n = ctypes.c_uint64(0)
+        _check(L.gg_stats_trace_get(self.h, None, None, 0, ctypes.byref(n)))
+        m, T = n.value, self.cfg.num_tiles
+        f = np.zeros((m, len(ST_FIELDS)), np.uint64)
+        h = np.zeros((m, T + 1), np.uint64)
+        if m:
+            _check(L.gg_stats_trace_get(self.h, f.ctypes.data_as(ctypes.c_void_p), h.ctypes.data_as(ctypes.c_void_p),
+                                        m, ctypes.byref(n)))
+        out = {name: f[:, i].copy() for i, name in enumerate(ST_FIELDS)}
+        out["sharer_hist"] = h
+        return out
+
+    def stats_trace_text(self, which):
+        """The text of network_utilization_memory.dat (ST_NETWORK_UTILIZATION)
+        or cache_line_replication.dat (ST_CACHE_LINE_REPLICATION) as the
+        reference writes it (gg_stats_trace_dump)."""
+        L = load()
+        need = ctypes.c_uint64(0)
+        _check(L.gg_stats_trace_dump(self.h, which, None, 0, ctypes.byref(need)))
+        buf = ctypes.create_string_buffer(need.value)
+        _check(L.gg_stats_trace_dump(self.h, which, buf, need.value, ctypes.byref(need)))
         return buf.value.decode()
 
     def queue_delay_batch(self, pkt_time, proc_time, min_processing_time=1):

@@ -3,6 +3,7 @@
 // gg_coherent_* / the round.  Device code and the design notes: gg_coh_dev.h;
 // the step and walker kernels: gg_coh_step.hip, gg_coh_walk.hip.
 #include "gg_coh_many.h"
+#include "gg_stats.h"
 
 #include <algorithm>
 #include <cmath>
@@ -691,6 +692,18 @@ static gg_status coh_check(gg_ctx* ctx)
                                       "tracking the miss_track_lines address table of a tile) was exceeded");
   if (e & GG_DERR_STATE) return gg_fail(GG_ERR_STATE, "coherent mode: a state the reference would reject "
                                         "(LOG_ASSERT_ERROR / assert; first at gg_coh_dev.h:%u)", ew[1]);
+  if (e & GG_DERR_SHARERS) return gg_fail(GG_ERR_STATE, "statistics trace: a directory entry holds more sharers than "
+                                          "there are tiles (the scan of gg_stats.hip)");
+  if (e & GG_DERR_SAMPLES) return gg_fail(GG_ERR_UNSUPPORTED, "statistics trace: the sample buffer is full "
+                                          "(max_samples of gg_stats_trace_configure); no sample was dropped silently");
+  return GG_OK;
+}
+
+gg_status gg_coh_launch_state(gg_ctx* ctx, const CP** P, const CS** S, bool* begun)
+{
+  hipSetDevice(ctx->device);
+  if (gg_status st = coh_alloc(ctx)) return st;
+  *P = &ctx->coh->P; *S = &ctx->coh->S; *begun = ctx->coh->begun;
   return GG_OK;
 }
 
@@ -737,6 +750,7 @@ gg_status gg_coherent_begin(gg_ctx* ctx, const gg_trace* tr, uint64_t* access_ou
   }
   GG_HIP(hipMemsetAsync(C->S.nxl, 0, sizeof(uint32_t) * std::max(P.nsx, 1u), s));
   GG_HIP(hipMemsetAsync(C->S.nyl, 0, sizeof(uint32_t) * std::max(P.nsy, 1u), s));
+  if (gg_status st = gg_stats_begin(ctx, s)) return st;   // (nothing without a configured statistics trace)
   hipLaunchKernelGGL(k_c_reset, dim3(P.L), dim3(256), 0, s, P, C->S, (const uint64_t*)C->offs_dev);
   GG_HIP(hipGetLastError());
   uint32_t hb = 0;
@@ -966,6 +980,12 @@ gg_status gg_coherent_run(gg_ctx* ctx, const gg_trace* tr, uint64_t* access_out_
   const char* nl_env = getenv("GG_COH_NO_LDS_CACHE");
   const bool plc = C->persist_lc && !(nl_env && atoi(nl_env));
   bool persist = P.L <= kPersistTiles && !P.mosi && !P.shl2 && !(np_env && atoi(np_env));   // (no persistent MOSI / sh_l2 instance)
+  // a statistics trace: one more launch per slot, the scan, which returns at
+  // once unless the slot ended a quantum with a sample due (gg_stats.hip); the
+  // per-step launches on every mesh size (a persistent launch holds cache
+  // state in LDS and runs many quanta: no point at which a scan could look)
+  const bool strace = gg_stats_on(ctx);
+  if (strace) persist = false;
   if (persist) {
     // the grid barrier needs every workgroup resident at once (a partitioned
     // device has fewer CUs): else the per-step launches
@@ -1007,6 +1027,7 @@ gg_status gg_coherent_run(gg_ctx* ctx, const gg_trace* tr, uint64_t* access_out_
         if (P.nsx) timed_launch(ctx, C, s, 1, [&] { launch_walk(C, s, P.nsx, C->wtx, L, 0, qend_walk); });
         if (P.nsy) timed_launch(ctx, C, s, 2, [&] { launch_walk(C, s, P.nsy, C->wty, L, 1, qend_walk && !P.nsx); });
       }
+      if (strace) if (gg_status e = gg_stats_slot(ctx, s, L)) return e;
     }
     GG_HIP(hipGetLastError());
     uint64_t done = 0;
@@ -1116,6 +1137,10 @@ gg_status gg_coherent_run_many(gg_ctx* const* ctxs, uint32_t n, const gg_trace* 
   if (n == 0) return gg_fail(GG_ERR_INVALID, "gg_coherent_run_many: n == 0");
   if (n > GG_MANY_MAX) return gg_fail(GG_ERR_INVALID, "gg_coherent_run_many: n = %u above GG_MANY_MAX = %u", n, (unsigned)GG_MANY_MAX);
   if (!ctxs || !traces) return gg_fail(GG_ERR_INVALID, "gg_coherent_run_many: NULL argument");
+  for (uint32_t i = 0; i < n; ++i)
+    if (ctxs[i] && gg_stats_on(ctxs[i]))
+      return gg_fail(GG_ERR_UNSUPPORTED, "gg_coherent_run_many: context %u has a statistics trace configured "
+                                         "(gg_coherent_run samples; turn it off with gg_stats_trace_configure(ctx, 0, 0, 0))", i);
   {
     std::vector<std::pair<const gg_ctx*, uint32_t>> seen(n);
     for (uint32_t i = 0; i < n; ++i) {

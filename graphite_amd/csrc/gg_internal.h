@@ -29,6 +29,8 @@
 #define GG_DERR_STATE 2u   // the reference would LOG_ASSERT_ERROR on this state
 #define GG_DERR_CAP 4u     // a device-side capacity (messages, queues, inbox) was exceeded
 #define GG_DERR_BARRIER 8u // a BARRIER record (GG_META_BARRIER) reached a path that has no barriers (Mode P)
+#define GG_DERR_SAMPLES 16u // the statistics trace's sample buffer is full (gg_stats.hip)
+#define GG_DERR_SHARERS 32u // the statistics trace's scan met a directory entry with more sharers than tiles
 
 // Geometry derived from gg_config (cache.cc:44, cache_hash_fn.h:11).
 struct gg_geom {
@@ -67,6 +69,7 @@ struct gg_timer {
 
 struct gg_noc_state;
 struct gg_coh_state;
+struct gg_stats_state;
 
 struct gg_ctx {
   gg_config cfg;
@@ -117,6 +120,8 @@ struct gg_ctx {
   // multi-rank round buffers (gg_round.hip), freed by gg_destroy
   void* round = nullptr;
   void (*round_free)(void*) = nullptr;
+  // statistics trace (gg_stats.hip), allocated by gg_stats_trace_configure
+  gg_stats_state* stats = nullptr;
 };
 inline void* gg_round_state(gg_ctx* ctx) { return ctx->round; }
 inline void gg_round_state_set(gg_ctx* ctx, void* p, void (*f)(void*)) { ctx->round = p; ctx->round_free = f; }
@@ -180,4 +185,9 @@ constexpr int kRwStepsShift = 33;
 gg_status gg_coh_import_slots(gg_ctx* ctx, const gg_cmsg* slots, uint32_t world, uint64_t region, uint64_t lo,
                               uint64_t hi, bool first, const uint64_t* skip_if_dev);
 gg_status gg_coh_check(gg_ctx* ctx);
+// statistics trace (gg_stats.hip; its view of the coherent state: gg_stats.h)
+void      gg_stats_free(gg_ctx* ctx);
+bool      gg_stats_on(const gg_ctx* ctx);                 // a trace is configured for the runs begun from now on
+gg_status gg_stats_begin(gg_ctx* ctx, hipStream_t s);     // gg_coherent_begin: the configured trace, no samples
+gg_status gg_stats_slot(gg_ctx* ctx, hipStream_t s, uint32_t L);   // gg_coherent_run: the scan launch of slot L
 uint64_t  gg_coh_generation(gg_ctx* ctx);    // bumped by every gg_coherent_begin (0: none yet)

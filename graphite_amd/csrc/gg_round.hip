@@ -399,6 +399,9 @@ gg_status gg_round_exchange(gg_ctx* ctx, void* nccl_comm, void* stream, uint64_t
 
 gg_status gg_coherent_run_ranks(gg_ctx* ctx, void* nccl_comm, const gg_trace* tr, uint64_t* access_out_dev, void* stream)
 {
+  if (ctx && gg_stats_on(ctx))       // the rounds do not sample: a rank samples its shards with gg_stats_trace_sample
+    return gg_fail(GG_ERR_UNSUPPORTED, "gg_coherent_run_ranks: a statistics trace is configured (drive the rounds with "
+                                       "gg_round_exchange and sample with gg_stats_trace_sample)");
   if (gg_status e = gg_coherent_begin(ctx, tr, access_out_dev, stream)) return e;
   uint64_t q = 0;
   for (;;) {

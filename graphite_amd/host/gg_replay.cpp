@@ -20,6 +20,13 @@
 //   gg_replay --coherent ... --table
 //       the tiles' summaries as TileManager::outputSummary's table
 //       (tile_manager_summary.cc:135-244) instead of one block per tile
+//   gg_replay --coherent ... --stats-trace DIR [--sampling-interval NS] [--max-samples M] [--protocol msi|mosi]
+//       the run's [statistics_trace] files DIR/network_utilization_memory.dat
+//       and DIR/cache_line_replication.dat (gg_stats_trace_*; the interval
+//       defaults to the reference's 10000 ns; the run fails when it needs
+//       more than M samples, default 4096), sampled on the device
+//   gg_replay --stats-trace-selftest
+//       prints both files' text for a fixed three-sample input (no GPU needed)
 //   gg_replay --format-table FILE...
 //       that table for per-tile summary texts read from the files
 //   gg_replay --tiles T --net M --route FILE
@@ -61,7 +68,9 @@ int main(int argc, char** argv)
   uint32_t tiles = 4, lines_log2 = 15, batches = 1, l2_assoc = 8, hot_lines = 64, net = GG_NET_EMESH_HOP_COUNTER;
   bool coherent = false, table = false;
   uint64_t per_tile = 100000;
-  std::string trace, id_file;
+  std::string trace, id_file, stats_dir;
+  uint64_t sampling_interval = 10000, max_samples = 4096;
+  uint32_t protocol = GG_PROTO_MSI;
   int ranks = 1, rank = 0;
   uint32_t shards = 1;
   for (int i = 1; i < argc; ++i) {
@@ -74,6 +83,26 @@ int main(int argc, char** argv)
     else if (a == "--l2-assoc") l2_assoc = (uint32_t)std::strtoul(next(), nullptr, 0);
     else if (a == "--trace") trace = next();
     else if (a == "--coherent") coherent = true;
+    else if (a == "--stats-trace") stats_dir = next();
+    else if (a == "--sampling-interval") sampling_interval = std::strtoull(next(), nullptr, 0);
+    else if (a == "--max-samples") max_samples = std::strtoull(next(), nullptr, 0);
+    else if (a == "--protocol") {
+      const std::string n = next();
+      if (n == "msi") protocol = GG_PROTO_MSI;
+      else if (n == "mosi") protocol = GG_PROTO_MOSI;
+      else { std::fprintf(stderr, "unknown protocol %s\n", n.c_str()); return 2; }
+    }
+    else if (a == "--stats-trace-selftest") {
+      // 4 application tiles (total_tiles 6), interval 1000 ns: a sample with
+      // shared lines, one standing for 3 sampling times, one with no shared line
+      const uint64_t f[3 * GG_NUM_ST_FIELDS] = {1000, 1, 322, 0, 194, 5, 6, 9, 12,
+                                                3000, 3, 7, 1, 6000, 2, 0, 4, 3,
+                                                6000, 1, 0, 0, 0, 3, 0, 3, 0};
+      const uint64_t h[3 * 5] = {0, 11, 2, 1, 1,  0, 4, 0, 1, 0,  0, 3, 0, 0, 0};
+      writeNetworkUtilizationTrace(std::cout, 6, 1000, f, 3);
+      writeCacheLineReplicationTrace(std::cout, 6, 4, f, h, 3);
+      return 0;
+    }
     else if (a == "--table") table = true;
     else if (a == "--format-table") {
       // TileManager::outputSummary's table of the per-tile summary texts in the files that follow
@@ -195,6 +224,11 @@ int main(int argc, char** argv)
       cfg.l2_assoc = l2_assoc;
       cfg.net_model = net;
       cfg.num_shards = shards;
+      cfg.protocol = protocol;
+      if (!stats_dir.empty() && !id_file.empty()) {
+        std::fprintf(stderr, "gg_replay: --stats-trace samples a single-process run\n");
+        return 2;
+      }
       if (!id_file.empty()) {
         // one process per GPU: the RCCL communicator of `ranks` processes
         if (rank < 0 || rank >= ranks || shards % (uint32_t)ranks) {
@@ -236,12 +270,29 @@ int main(int argc, char** argv)
       std::vector<uint64_t> offs(tiles + 1);
       for (uint32_t t = 0; t <= tiles; ++t) offs[t] = (uint64_t)t * per_tile;
       gg_trace tr{addr.p, meta.p, offs.data(), n};
+      if (!stats_dir.empty())
+        check(gg_stats_trace_configure(be.ctx(), GG_ST_NETWORK_UTILIZATION | GG_ST_CACHE_LINE_REPLICATION, sampling_interval,
+                                       max_samples), "gg_stats_trace_configure");
       if (comm) check(gg_coherent_run_ranks(be.ctx(), comm, &tr, nullptr, nullptr), "gg_coherent_run_ranks");
       else check(gg_coherent_run(be.ctx(), &tr, nullptr, nullptr), "gg_coherent_run");
       std::vector<uint64_t> st((size_t)tiles * GG_NUM_TILE_STATS), cc((size_t)tiles * 2 * GG_NUM_CACHE_COUNTERS),
           nc((size_t)tiles * GG_NUM_NET_COUNTERS);
       check(gg_coherent_get_stats(be.ctx(), st.data(), cc.data(), nullptr), "gg_coherent_get_stats");
       check(gg_noc_get_counters(be.ctx(), nc.data()), "gg_noc_get_counters");
+      if (!stats_dir.empty()) {
+        const char* names[2] = {"network_utilization_memory.dat", "cache_line_replication.dat"};
+        const int which[2] = {GG_ST_NETWORK_UTILIZATION, GG_ST_CACHE_LINE_REPLICATION};
+        for (int k = 0; k < 2; ++k) {
+          uint64_t need = 0;
+          check(gg_stats_trace_dump(be.ctx(), which[k], nullptr, 0, &need), "gg_stats_trace_dump");
+          std::string text(need, '\0');
+          check(gg_stats_trace_dump(be.ctx(), which[k], &text[0], need, &need), "gg_stats_trace_dump");
+          text.resize(need - 1);
+          std::ofstream f(stats_dir + "/" + names[k], std::ios::binary);
+          if (!f) { std::fprintf(stderr, "gg_replay: cannot write %s/%s\n", stats_dir.c_str(), names[k]); return 1; }
+          f << text;
+        }
+      }
       if (comm) {
         // every statistic is kept by the rank owning its tile: the node's totals are the sums
         for (std::vector<uint64_t>* v : {&st, &cc, &nc}) {

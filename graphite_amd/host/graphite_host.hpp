@@ -559,6 +559,75 @@ inline std::string formatTileSummaries(const std::vector<std::string>& summaries
   return out.str();
 }
 
+// ---- [statistics_trace] files from gg_stats_trace_get's integers ---------
+// fields: [n][GG_NUM_ST_FIELDS]; a sample with repeat r stands for r
+// consecutive sampling times (the quanta between them were empty): the
+// later ones have zero utilisation and the same replication state.
+//
+// network_utilization_memory.dat (Network::outputUtilizationSummary,
+// network.cc:608-641): one line per sampling time, the flits sent, broadcast
+// and received in the interval over total_tiles * sampling_interval.
+inline void writeNetworkUtilizationTrace(std::ostream& out, uint32_t total_tiles, uint64_t sampling_interval_ns,
+                                         const uint64_t* fields, uint64_t n)
+{
+  const double denom = (double)((int64_t)total_tiles * (int64_t)sampling_interval_ns);
+  for (uint64_t i = 0; i < n; ++i) {
+    const uint64_t* f = fields + i * GG_NUM_ST_FIELDS;
+    for (uint64_t r = 0; r < f[GG_STF_REPEAT]; ++r) {
+      const double s = ((double)(r ? 0 : f[GG_STF_FLITS_SENT])) / denom;
+      const double b = ((double)(r ? 0 : f[GG_STF_FLITS_BROADCASTED])) / denom;
+      const double v = ((double)(r ? 0 : f[GG_STF_FLITS_RECEIVED])) / denom;
+      out << s << ", " << b << ", " << v << std::endl;
+    }
+  }
+}
+
+// cache_line_replication.dat (MemoryManager::outputCacheLineReplicationSummary,
+// …mosi/memory_manager.cc:491-602): per sampling time the L1 and L2 line
+// counts, the sharer histogram over 1..total_tiles, the replication-degree
+// vector over 1..2*total_tiles, and a blank line.  sharer_hist:
+// [n][num_tiles + 1].  The degree vector is the reference's double
+// arithmetic (:563-599) on the raw counts.  Where the reference's values are
+// undefined this writer differs on purpose: with no shared L2 line its ratio
+// is 0/0 (or x/0) and the casts of floor / ceil of it index the vector with
+// an undefined value — here a ratio over zero shared L2 lines is 0, empty
+// bins are skipped (they add 0 wherever they land) and an index beyond
+// 2 * total_tiles is dropped instead of written out of bounds.
+inline void writeCacheLineReplicationTrace(std::ostream& out, uint32_t total_tiles, uint32_t num_tiles,
+                                           const uint64_t* fields, const uint64_t* sharer_hist, uint64_t n)
+{
+  for (uint64_t i = 0; i < n; ++i) {
+    const uint64_t* f = fields + i * GG_NUM_ST_FIELDS;
+    const uint64_t ex1 = f[GG_STF_L1_EXCLUSIVE], sh1 = f[GG_STF_L1_SHARED];
+    const uint64_t ex2 = f[GG_STF_L2_EXCLUSIVE], sh2 = f[GG_STF_L2_SHARED];
+    std::ostringstream os;
+    std::vector<uint64_t> count(total_tiles + 1, 0);
+    for (uint32_t k = 1; k <= num_tiles && k <= total_tiles; ++k) count[k] = sharer_hist[i * (num_tiles + 1) + k];
+    os << ex1 << ", " << sh1 << ", " << std::endl;
+    os << ex2 << ", " << sh2 << ", " << std::endl;
+    for (uint32_t k = 1; k <= total_tiles; ++k) os << count[k] << ", ";
+    os << std::endl;
+    std::vector<uint64_t> repl(2 * (size_t)total_tiles + 1, 0);
+    repl[1] += ex2 - ex1;
+    if (repl.size() > 2) repl[2] += ex1;
+    count[1] -= ex2;
+    const double ratio = sh2 ? 1.0 * sh1 / sh2 : 0.0;
+    for (uint32_t k = 1; k <= total_tiles; ++k) {
+      const uint64_t lines = count[k];
+      if (lines == 0) continue;
+      const double degree_L1 = ratio * (int32_t)k;
+      const uint64_t num_low = (uint64_t)(lines * (ceil(degree_L1) - degree_L1));
+      const int64_t degree_low = (int32_t)floor(degree_L1), degree_high = (int32_t)ceil(degree_L1);
+      const uint64_t num_high = lines - num_low;
+      if (k + degree_low < (int64_t)repl.size()) repl[k + degree_low] += num_low;
+      if (k + degree_high < (int64_t)repl.size()) repl[k + degree_high] += num_high;
+    }
+    for (size_t k = 1; k < repl.size(); ++k) os << repl[k] << ", ";
+    os << std::endl << std::endl;
+    for (uint64_t r = 0; r < f[GG_STF_REPEAT]; ++r) out << os.str();
+  }
+}
+
 // One cache (tile, level) of a Backend with the reference Cache API.
 class Cache {
  public:

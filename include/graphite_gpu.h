@@ -651,6 +651,73 @@ gg_status gg_coherent_get_protocol_stats(gg_ctx* ctx, uint64_t* out);
 enum { GG_SUMMARY_BLOCKS = 0, GG_SUMMARY_TABLE = 1 };
 gg_status gg_dump_summary(gg_ctx* ctx, int format, char* buf, uint64_t cap, uint64_t* needed);
 
+/* The [statistics_trace] time series of a coherent run (carbon_sim.cfg:396-411;
+ * StatisticsThread, statistics_thread.cc:65-75: one sample whenever the lax
+ * barrier releases at a multiple of sampling_interval).  Two statistics:
+ *   GG_ST_NETWORK_UTILIZATION    network_utilization_memory.dat (network.cc:
+ *     608-641): the flits sent, broadcast and received since the previous
+ *     sample, summed over the tiles;
+ *   GG_ST_CACHE_LINE_REPLICATION cache_line_replication.dat (…mosi/
+ *     memory_manager.cc:491-602): the L1-D and L2 lines that are exclusive
+ *     (MODIFIED) or shared (OWNED + SHARED) and the directories' histogram
+ *     "entries with n sharers" (Directory::updateSharerStats, directory.cc:
+ *     58-80; entries on the replaced list count until their NULLIFY ends).
+ *     The L1-I is not simulated and contributes 0.
+ * gg_stats_trace_configure sets the trace of the runs begun afterwards
+ * (gg_coherent_begin / _run); statistics = 0 turns it off.  GG_ERR_INVALID:
+ * an unknown statistics bit, an interval of 0 or not a multiple of
+ * cfg.quantum_ns (carbon_sim.cfg:399), max_samples = 0 or a sample buffer
+ * (max_samples * (GG_NUM_ST_FIELDS + num_tiles + 1) * 8 bytes, allocated whole
+ * and zeroed at every begin) above GG_ST_MAX_BUFFER_BYTES.  GG_ERR_UNSUPPORTED:
+ * cache_line_replication under the shared-L2 protocols (the reference has it
+ * for pr_l1_pr_l2_dram_directory_mosi only, memory_manager.cc:200-212; MSI is
+ * an extension here: same private-L2 formula, same data layout).
+ * Sampling.  gg_coherent_run samples on the device, with no host round trip:
+ * when quantum q ends and the run continues at quantum q' (empty quanta are
+ * skipped), the lax barrier has passed the times (q+1)*quantum_ns ...
+ * q'*quantum_ns; if multiples of the interval are among them, ONE sample is
+ * taken of the state after q's last step: time_ns = the first such multiple,
+ * repeat = how many there are (nothing happens in a skipped quantum: the
+ * repeats are zero utilisation and the same replication state).  At the
+ * run's last quantum only its own barrier counts (a partial last interval is
+ * not emitted).  While a trace is configured gg_coherent_run uses the
+ * per-step launches on every mesh size (the persistent small-mesh kernel
+ * keeps cache state in LDS where a scan cannot see it); results are
+ * bit-identical.  With no trace configured nothing changes: the same
+ * launches, the same kernels.  gg_coherent_run_many and gg_coherent_run_ranks
+ * return GG_ERR_UNSUPPORTED for a context with a trace configured (the counts
+ * are additive over contexts: a rank samples its own shards with
+ * gg_stats_trace_sample).
+ * gg_stats_trace_sample appends one sample (repeat 1) of the context's
+ * current state at barrier_time_ns: between the quanta of a host-driven run
+ * (gg_coherent_quantum), or after a finished gg_coherent_run for the
+ * end-of-run state.  Synchronizes.
+ * A full sample buffer is an error (GG_ERR_UNSUPPORTED from the run or from
+ * gg_stats_trace_sample), never a silently dropped sample.
+ * gg_stats_trace_get: *count = samples taken; the first min(*count, cap)
+ * samples into fields [cap][GG_NUM_ST_FIELDS] and sharer_hist
+ * [cap][num_tiles + 1] (bin n = directory entries with n sharers, bin 0
+ * unused; either may be NULL).  The integers are the contract: rates and
+ * text derive from them on the host.
+ * gg_stats_trace_dump: the text of one file (`which` = one GG_ST_* bit), as
+ * the reference writes it (default ostream formatting, ", " separators with
+ * the trailing ones, a blank line after each replication sample, vectors over
+ * total_tiles = cfg.total_tiles or num_tiles + 2, and 2 * total_tiles);
+ * buffer protocol as gg_dump_summary.  The replication-degree line is
+ * computed from the raw counts in the reference's double arithmetic
+ * (memory_manager.cc:563-599); where the reference indexes with an undefined
+ * value (no shared L2 line: 0/0; an empty bin is harmless there only by
+ * luck) empty bins are skipped and a ratio over zero shared L2 lines is 0. */
+enum { GG_ST_NETWORK_UTILIZATION = 1, GG_ST_CACHE_LINE_REPLICATION = 2 };
+#define GG_ST_MAX_BUFFER_BYTES (1ull << 30)
+enum { GG_STF_TIME_NS = 0, GG_STF_REPEAT, GG_STF_FLITS_SENT, GG_STF_FLITS_BROADCASTED, GG_STF_FLITS_RECEIVED,
+       GG_STF_L1_EXCLUSIVE, GG_STF_L1_SHARED, GG_STF_L2_EXCLUSIVE, GG_STF_L2_SHARED, GG_NUM_ST_FIELDS };
+gg_status gg_stats_trace_configure(gg_ctx* ctx, uint32_t statistics, uint64_t sampling_interval_ns,
+                                   uint64_t max_samples);
+gg_status gg_stats_trace_sample(gg_ctx* ctx, uint64_t barrier_time_ns);
+gg_status gg_stats_trace_get(gg_ctx* ctx, uint64_t* fields, uint64_t* sharer_hist, uint64_t cap, uint64_t* count);
+gg_status gg_stats_trace_dump(gg_ctx* ctx, int which, char* buf, uint64_t cap, uint64_t* needed);
+
 /* Synthetic workload generator (not part of the reference boundary; the
  * reference has no trace capture): fills a tile-major trace of
  * `per_tile` records for tiles [tile_begin, tile_begin + tiles) with the
