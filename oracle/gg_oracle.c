@@ -26,6 +26,8 @@ static int ceil_log2(uint32_t n) { int p = floor_log2(n); return ((1u << p) == n
 /* misc/time_types.h:81-109 */
 static uint64_t lat_to_ps(uint64_t cycles, double f) { return (uint64_t)ceil(((double)1000 * cycles) / (double)f); }
 static uint64_t time_to_cycles(uint64_t ps, double f) { return (uint64_t)ceil(((double)ps * (double)f) / (double)1.0e3); }
+uint64_t oracle_lat_to_ps(uint64_t cycles, double frequency_ghz) { return lat_to_ps(cycles, frequency_ghz); }
+uint64_t oracle_time_to_cycles(uint64_t ps, double frequency_ghz) { return time_to_cycles(ps, frequency_ghz); }
 
 /* ======================================================================== */
 /* Synthetic workloads        */

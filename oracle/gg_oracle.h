@@ -27,6 +27,10 @@ extern "C" {
 
 /* ---------------- synthetic trace generators -------- */
 uint64_t oracle_splitmix64_at(uint64_t seed, uint64_t i);
+/* Latency::toPicosec / Time::toCycles (time_types.h:81-109) as every model
+ * of the oracle uses them, for the fixture test of the two conversions.    */
+uint64_t oracle_lat_to_ps(uint64_t cycles, double frequency_ghz);
+uint64_t oracle_time_to_cycles(uint64_t ps, double frequency_ghz);
 /* configs[1]: uniform private region of 2^lines_log2 lines per tile at
  * byte base tile << base_shift, WRITE iff ((z >> 32) % 3) == 0.             */
 void oracle_gen_uniform(uint32_t tile, uint64_t first, uint64_t n,

@@ -39,6 +39,9 @@ def lib():
         vp = ctypes.c_void_p
         L.oracle_splitmix64_at.restype = ctypes.c_uint64
         L.oracle_splitmix64_at.argtypes = [ctypes.c_uint64, ctypes.c_uint64]
+        for n in ("oracle_lat_to_ps", "oracle_time_to_cycles"):
+            getattr(L, n).restype = ctypes.c_uint64
+            getattr(L, n).argtypes = [ctypes.c_uint64, ctypes.c_double]
         L.oracle_gen_uniform.argtypes = [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64,
                                          ctypes.c_uint32, ctypes.c_uint32, _u64p, _u32p]
         L.oracle_cache_create.restype = vp

@@ -145,6 +145,7 @@ struct HCfg {
   UInt64 quantum_ps;
   UInt32 l2_assoc;            // l2_cache/T1/associativity (carbon_sim.cfg:233: 8; configs[4]: 16)
   UInt32 workload;            // 0 hotspot (configs[2..3]), 1 stress (configs[4])
+  double f;                   // the one DVFS domain's frequency in GHz (carbon_sim.cfg: 1.0)
 };
 static HCfg H;
 
@@ -272,7 +273,7 @@ Cache::Cache(string name, CachingProtocolType cpt, CacheCategory cat, SInt32 lev
   _log_line_size = floorLog2(_line_size);
   _sets = new CacheSet*[_num_sets];
   for (UInt32 i = 0; i < _num_sets; i++) _sets[i] = new CacheSet(i, cpt, level, _replacement_policy, _associativity, _line_size);
-  _frequency = 1.0; _voltage = 1.0;                                    // initializeDVFS: the 1 GHz domain
+  _frequency = H.f; _voltage = 1.0;                                    // initializeDVFS: the one domain (1 GHz unless the case says so)
   _perf_model = CachePerfModel::create(perf_model_type, data_lat, tags_lat, _frequency);
   ccount(this);
 }
@@ -371,7 +372,7 @@ DirectoryCache::DirectoryCache(Tile* tile, CachingProtocolType cpt, string dts, 
   UInt32 max_application_sharers = Config::getSingleton()->getApplicationTiles();
   UInt32 entry_size = ceil(1.0 * DirectoryEntry::getSize(_directory_type, hw, max_application_sharers) / 8);
   _directory_size = _total_entries * entry_size;
-  _frequency = 1.0; _voltage = 1.0;
+  _frequency = H.f; _voltage = 1.0;
   _directory_access_cycles = computeDirectoryAccessCycles();
   _directory_access_latency = Time(Latency(_directory_access_cycles, _frequency));
   _synchronization_delay = Time(Latency(DVFSManager::getSynchronizationDelay(), _frequency));
@@ -805,7 +806,7 @@ static UInt32 modeled_bits(UInt32 type)        // network_model.cc:185-200 + shm
   bool data = type == 6 || type == 7 || type == 10 || type == 11 || type == 15 || type == 16 || type == 18;   // EX_REP, SH_REP, FLUSH_REP, WB_REP, DRAM_STORE_REQ, DRAM_FETCH_REP, SH_REP_EX (DOWNGRADE_REP: no data buffer)
   return 2 * idb + 4 + 48 + (data ? 512 : 0) + (type == 13 ? idb : 0);   // INV_FLUSH_COMBINED_REQ: + single receiver
 }
-static UInt64 lat_ps(UInt64 cycles) { return (UInt64)ceil(((double)1000 * cycles) / 1.0); }
+static UInt64 lat_ps(UInt64 cycles) { return Latency(cycles, H.f).toPicosec(); }
 // emesh_hop_counter (network_model_emesh_hop_counter.cc:143-157) / magic + serialization (network_model.cc:142-150)
 static void route(HMsg& m)
 {
@@ -1020,10 +1021,10 @@ template <class V> static void read_raw(const string& path, V& v)
 
 static void run_case(FILE* man, bool first, const char* name, UInt32 T, UInt32 N, UInt32 hot, UInt32 K, UInt32 net,
                      UInt32 dir_entries, UInt32 dir_assoc, UInt32 l2_assoc = 8, UInt32 workload = 0,
-                     const RawTrace* raw = NULL)
+                     const RawTrace* raw = NULL, double frequency = 1.0)
 {
   H.T = T; H.K = K; H.net = net; H.dir_entries = dir_entries; H.dir_assoc = dir_assoc; H.quantum_ps = 1000000;
-  H.l2_assoc = l2_assoc; H.workload = workload;
+  H.l2_assoc = l2_assoc; H.workload = workload; H.f = frequency;
   build_shard_map();
   g_t.clear(); g_t.resize(T); g_step.clear(); g_bnd.clear(); g_cc.clear(); g_dc.clear(); g_dram.clear();
   vector<UInt64> offs(T + 1);
@@ -1118,10 +1119,12 @@ static void run_case(FILE* man, bool first, const char* name, UInt32 T, UInt32 N
 #endif
   fprintf(man, "%s  \"%s\": {\"tiles\": %u, \"per_tile\": %u, \"hot_lines\": %u, \"num_shards\": %u, \"net\": %u, "
           "\"dir_entries\": %u, \"dir_assoc\": %u, \"l2_assoc\": %u, \"workload\": \"%s\", \"records\": %llu, "
-          "\"quanta\": %llu, \"steps\": %llu}",
+          "\"quanta\": %llu, \"steps\": %llu",
           first ? "" : ",\n", name, T, N, hot, K, net, dir_entries, dir_assoc, l2_assoc,
           workload == 2 ? "fft_real_p16_m10" : workload ? "stress" : "hotspot", (unsigned long long)nrec,
           (unsigned long long)quanta, (unsigned long long)steps);
+  if (frequency != 1.0) fprintf(man, ", \"frequency_ghz\": %.17g", frequency);   // absent: 1.0
+  fprintf(man, "}");
   printf("  coh %-10s tiles %u x %u: %llu quanta, %llu steps\n", name, T, N, (unsigned long long)quanta,
          (unsigned long long)steps);
   for (UInt32 t = 0; t < T; ++t) delete g_t[t].tile;
@@ -1157,6 +1160,12 @@ int main(int argc, char** argv)
   // NULLIFY of sharers and owners, DRAM stores
   run_case(man, false, N("evict16"), 16, 12000, 64, 1, 1, 0, 16, 2);
   run_case(man, false, N("evict16s4"), 16, 12000, 64, 4, 1, 0, 16, 2);
+  // off the 1 GHz square-mesh point: 1.5 GHz (Latency::toPicosec rounds up),
+  // a 3 x 4 mesh, and an 8 x 9 mesh (7 tile-id bits, two sharer words) in 8
+  // shards at 2.66 GHz
+  run_case(man, false, N("hot16f15"), 16, 300, 8, 1, 1, 0, 16, 8, 0, NULL, 1.5);
+  run_case(man, false, N("hot12"), 12, 300, 8, 1, 1, 0, 16);
+  run_case(man, false, N("shard72f266"), 72, 100, 16, 8, 1, 0, 16, 8, 0, NULL, 2.66);
   if (argc > 2) {
     RawTrace fft;
     read_raw(string(argv[2]) + ".addr", fft.addr);
@@ -1187,6 +1196,12 @@ int main(int argc, char** argv)
   // MODIFIED / OWNED lines, INV_REP of SHARED ones, "just an eviction" writes
   run_case(man, false, "mosi_evict16", 16, 12000, 64, 1, 1, 0, 16);
   run_case(man, false, "mosi_evict16s4", 16, 12000, 64, 4, 1, 0, 16);
+  // off the 1 GHz square-mesh point: 1.5 GHz (Latency::toPicosec rounds up),
+  // a 3 x 4 mesh, and an 8 x 9 mesh (7 tile-id bits, two sharer words) in 8
+  // shards at 2.66 GHz
+  run_case(man, false, "mosi_hot16f15", 16, 300, 8, 1, 1, 0, 16, 8, 0, NULL, 1.5);
+  run_case(man, false, "mosi_hot12", 12, 300, 8, 1, 1, 0, 16);
+  run_case(man, false, "mosi_shard72f266", 72, 100, 16, 8, 1, 0, 16, 8, 0, NULL, 2.66);
   if (argc > 2) {
     RawTrace fft;
     read_raw(string(argv[2]) + ".addr", fft.addr);
@@ -1221,6 +1236,12 @@ int main(int argc, char** argv)
   // tools/fft_trace (tests/golden/fft_real_p16_m10.npz, accesses only: the
   // BARRIER release is restated, not the reference's SyncServer), 16 tiles,
   // emesh_hop_counter; exported to raw files by make_golden.sh
+  // off the 1 GHz square-mesh point: 1.5 GHz (Latency::toPicosec rounds up),
+  // a 3 x 4 mesh, and an 8 x 9 mesh (7 tile-id bits, two sharer words) in 8
+  // shards at 2.66 GHz
+  run_case(man, false, "hot16f15", 16, 300, 8, 1, 1, 0, 16, 8, 0, NULL, 1.5);
+  run_case(man, false, "hot12", 12, 300, 8, 1, 1, 0, 16);
+  run_case(man, false, "shard72f266", 72, 100, 16, 8, 1, 0, 16, 8, 0, NULL, 2.66);
   if (argc > 2) {
     RawTrace fft;
     read_raw(string(argv[2]) + ".addr", fft.addr);

@@ -16,6 +16,7 @@
 //                                 .../pr_l1_pr_l2_dram_directory_msi/cache_line_info.cc
 //   IntervalTree                  common/misc/interval_tree.cc
 //   QueueModelMG1                 common/shared_models/queue_models/queue_model_m_g_1.cc
+//   Latency, Time                 common/misc/time_types.h
 //
 // The thin glue the reference keeps in files that cannot be compiled here
 // (Cache in cache.cc, the L1/L2 controllers, QueueModelHistoryTree) is
@@ -37,6 +38,7 @@
 #include "pr_l1_pr_l2_dram_directory_msi/cache_line_info.h"
 #include "interval_tree.h"
 #include "queue_model_m_g_1.h"
+#include "time_types.h"
 
 using namespace std;
 
@@ -432,6 +434,46 @@ static void gen_modep(const char* name, int gen, uint32_t tiles, uint32_t per_ti
   manifest(s);
 }
 
+// Latency::toPicosec / Time::toCycles (common/misc/time_types.h:81-109), the
+// two conversions every timing expression goes through, at clock frequencies
+// where 1000 / f is an integer (1.0, 2.0) and where it is not.  File layout:
+// the cycle counts, the picosecond values, then per frequency
+// Latency(c, f).toPicosec() of every cycle count, then per frequency
+// Time(p).toCycles(f) of every picosecond value.
+static void gen_timeconv(const char* name) {
+  static const char* kF[] = {"0.75", "1.0", "1.5", "2.0", "2.66", "3.0"};
+  const int nf = (int)(sizeof(kF) / sizeof(kF[0]));
+  vector<UInt64> cyc, ps;
+  static const UInt64 kC[] = {0, 1, 2, 3, 7, 8, 133, 999, 1000, 1001, 1000003};
+  for (size_t i = 0; i < sizeof(kC) / sizeof(kC[0]); ++i) cyc.push_back(kC[i]);
+  for (int k = -3; k <= 3; ++k) { cyc.push_back((1ull << 32) + k); cyc.push_back((1ull << 40) + k); }
+  for (int i = 0; i < 240; ++i) cyc.push_back(sm_at(21, (uint64_t)i) >> (24 + i % 40));     // up to 40 bits
+  // whole numbers of periods of every frequency above (3 cycles of 1.5 GHz =
+  // 2000 ps, of 0.75 GHz = 4000 ps; 133 cycles of 2.66 GHz = 50000 ps) and
+  // their neighbours
+  static const UInt64 kP[] = {500, 1000, 2000, 4000, 50000}, kM[] = {1, 2, 3, 7, 133, 1000, 999983};
+  ps.push_back(0); ps.push_back(1); ps.push_back(999);
+  for (size_t i = 0; i < sizeof(kP) / sizeof(kP[0]); ++i)
+    for (size_t j = 0; j < sizeof(kM) / sizeof(kM[0]); ++j)
+      for (int k = -1; k <= 1; ++k) ps.push_back(kP[i] * kM[j] + k);
+  for (int k = -3; k <= 3; ++k) { ps.push_back((1ull << 40) + k); ps.push_back((1ull << 50) + k); }
+  for (int i = 0; i < 200; ++i) ps.push_back(sm_at(22, (uint64_t)i) >> (14 + i % 50));      // up to 50 bits
+  vector<UInt64> rows(cyc);
+  rows.insert(rows.end(), ps.begin(), ps.end());
+  for (int f = 0; f < nf; ++f)
+    for (size_t i = 0; i < cyc.size(); ++i) rows.push_back(Latency(cyc[i], strtod(kF[f], NULL)).toPicosec());
+  for (int f = 0; f < nf; ++f)
+    for (size_t i = 0; i < ps.size(); ++i) rows.push_back(Time(ps[i]).toCycles(strtod(kF[f], NULL)));
+  char file[256]; snprintf(file, sizeof file, "%s.u64", name);
+  write_bin(file, rows.data(), rows.size() * 8);
+  string s = string("\"") + name + "\": {\"file\": \"" + file + "\", \"kind\": \"timeconv\", \"frequencies\": [";
+  for (int f = 0; f < nf; ++f) s += string(f ? ", " : "") + kF[f];
+  char m[256];
+  snprintf(m, sizeof m, "], \"cycles\": %u, \"picoseconds\": %u, \"source\": \"common/misc/time_types.h:81-109\"}",
+           (unsigned)cyc.size(), (unsigned)ps.size());
+  manifest(s + m);
+}
+
 int main(int argc, char** argv) {
   CHECK(argc == 2);
   g_dir = argv[1];
@@ -478,6 +520,8 @@ int main(int argc, char** argv) {
   gen_modep("modep_mixed", 1, 3, 50000, 13, 32, 4, "lru", 512, 8, "lru");
   gen_modep("modep_small", 1, 3, 40000, 11, 4, 2, "lru", 16, 4, "lru");
   gen_modep("modep_rr", 1, 2, 40000, 12, 8, 4, "round_robin", 64, 8, "round_robin");
+  // 5. the cycle <-> picosecond conversions of time_types.h
+  gen_timeconv("timeconv");
 
   fprintf(g_manifest, "\n}\n");
   fclose(g_manifest);

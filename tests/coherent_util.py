@@ -1,8 +1,10 @@
 """Test helpers for the coherent mode: the oracle as a `graphite_amd.coherent`
-engine (CPU), and the invariants every coherent run must satisfy."""
+engine (CPU), the invariants every coherent run must satisfy, and the
+GPU-against-oracle comparison of one run (_gpu_run / _oracle_run / _compare)."""
 import numpy as np
 
 from graphite_amd import config as C
+from tests.gpu_util import torch_dev, to_dev, to_np
 
 
 class OracleEngine:
@@ -58,3 +60,37 @@ def check_invariants(stats, cache, out, offs, per_tile_expected=None):
     reps = S["sent_ex_rep"].sum() + S["sent_sh_rep"].sum() + S["sent_upgrade_rep"].sum()
     assert reps == reqs.sum()
     assert S["msgs_sent"].sum() == S["msgs_received"].sum()
+
+
+def _gpu_run(cfg, a, m, o):
+    torch = torch_dev()
+    from graphite_amd import backend as B
+    be = B.Backend(cfg)
+    addr, meta = to_dev(torch, a, torch.int64), to_dev(torch, m, torch.int32)
+    out = torch.zeros(len(a), dtype=torch.int64, device="cuda")
+    be.coherent_run(addr, meta, o, out)
+    torch.cuda.synchronize()
+    st, cc, ri = be.coherent_stats()
+    return to_np(out, np.uint64), st, cc, be.noc_counters(), ri
+
+
+def _oracle_run(cfg, a, m, o):
+    from oracle import pyoracle as po
+    oc = po.OracleCoherent(cfg)
+    out = oc.run(a, m, o)
+    return out, oc.tile_stats(), oc.cache_counters(), oc.net_counters(), oc.run_info()
+
+
+def _compare(cfg, a, m, o):
+    g = _gpu_run(cfg, a, m, o)
+    r = _oracle_run(cfg, a, m, o)
+    for name, x, y in zip(("access words", "tile stats", "cache counters", "noc counters"), g[:4], r[:4]):
+        if not np.array_equal(x, y):
+            d = np.argwhere(np.asarray(x) != np.asarray(y))
+            raise AssertionError("%s differ at %d places, first %s: gpu %s oracle %s"
+                                 % (name, len(d), d[0], np.asarray(x)[tuple(d[0])], np.asarray(y)[tuple(d[0])]))
+    for k in ("steps", "net_msgs", "self_msgs", "boundary_msgs"):
+        i = C.RUN_INFO.index(k)
+        assert g[4][i] == r[4][i], (k, g[4][i], r[4][i])
+    check_invariants(g[1], g[2], g[0], o, per_tile_expected=int(o[1] - o[0]))
+    return g

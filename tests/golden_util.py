@@ -38,6 +38,20 @@ def compact_code(res):
     return out
 
 
+def timeconv():
+    """(frequencies, cycles[nc], picoseconds[np], to_ps[nf][nc], to_cycles[nf][np])
+    of the "timeconv" fixture: Latency(c, f).toPicosec() and Time(p).toCycles(f)
+    of the reference's time_types.h (oracle/ref/ref_harness.cc, gen_timeconv)."""
+    e = manifest()["timeconv"]
+    rows = load(e["file"], np.uint64)
+    nf, nc, npz = len(e["frequencies"]), e["cycles"], e["picoseconds"]
+    assert len(rows) == (nc + npz) * (nf + 1)
+    cyc, ps = rows[:nc], rows[nc:nc + npz]
+    to_ps = rows[nc + npz:nc + npz + nf * nc].reshape(nf, nc)
+    to_cyc = rows[nc + npz + nf * nc:].reshape(nf, npz)
+    return e["frequencies"], cyc, ps, to_ps, to_cyc
+
+
 def coh_manifest():
     with open(os.path.join(GOLDEN, "coh_manifest.json")) as f:
         return json.load(f)
@@ -70,7 +84,7 @@ def coh_case(name, m):
     kw = dict(num_shards=m["num_shards"], net_model=C.NET_EMESH_HOP_COUNTER if m["net"] == 1 else C.NET_MAGIC)
     if m["dir_entries"]:
         kw.update(dir_total_entries=m["dir_entries"], dir_assoc=m["dir_assoc"])
-    kw.update(l2_assoc=m.get("l2_assoc", 8))
+    kw.update(l2_assoc=m.get("l2_assoc", 8), frequency_ghz=m.get("frequency_ghz", 1.0))
     mosi = name.startswith("mosi_")
     if mosi:
         kw.update(protocol=C.PROTO_MOSI)

@@ -173,6 +173,29 @@ def test_hop_by_hop_different_settings():
 
 
 @pytest.mark.gpu
+def test_hop_by_hop_different_clocks_and_dram_bandwidths():
+    """T=16, K=1: three instances that differ only in frequency_ghz (1.0, 1.5,
+    2.66: the exact and the rounding forms of the cycle <-> picosecond
+    conversions side by side in one launch set) and dram_bandwidth; each
+    equals the oracle and its own lone coherent_run."""
+    specs = [_spec(16, 1, HBH, 300, trace=dict(hot_lines=8), cfg=dict(frequency_ghz=f, dram_bandwidth=bw))
+             for f, bw in ((1.0, 5.0), (1.5, 3.3), (2.66, 64.0))]
+    torch = torch_dev()
+    en, lone = _Ensemble(torch, specs), _Ensemble(torch, specs)
+    try:
+        assert en.run() == [0, 0, 0]
+        for i, s in enumerate(specs):
+            r = en.result(i)
+            _same(r, _oracle(s), "instance %d vs oracle" % i)
+            lone.single(i)
+            _same(lone.result(i), r, "lone run %d vs ensemble" % i)
+        assert not np.array_equal(en.result(0)[0], en.result(1)[0])
+    finally:
+        en.close()
+        lone.close()
+
+
+@pytest.mark.gpu
 def test_hop_by_hop_256_tiles_and_lone_run():
     """T=256, K=8 (the per-step path in a single run too), two instances x 150
     records; each also equals a lone coherent_run on a fresh context."""

@@ -47,6 +47,26 @@ def test_other_queue_models_reference_sequences(name):
         assert h.analytical_requests == e["analytical_requests"]
 
 
+def test_time_conversions_match_reference():
+    """The oracle's lat_to_ps / time_to_cycles == Latency::toPicosec /
+    Time::toCycles of the reference's time_types.h (tests/golden/timeconv.u64)
+    at 0.75, 1.0, 1.5, 2.0, 2.66 and 3.0 GHz."""
+    freqs, cyc, ps, to_ps, to_cyc = G.timeconv()
+    assert freqs == [0.75, 1.0, 1.5, 2.0, 2.66, 3.0]
+    assert {0, 1, 7, 999, 1000003, 1 << 32, 1 << 40} <= set(cyc.tolist())
+    assert {1 << 40, 1 << 50, 2000, 1999, 2001, 50000, 49999, 50001} <= set(ps.tolist())
+    L = po.lib()
+    for i, f in enumerate(freqs):
+        got = np.array([L.oracle_lat_to_ps(int(c), f) for c in cyc], np.uint64)
+        np.testing.assert_array_equal(got, to_ps[i], err_msg="lat_to_ps at %s GHz" % f)
+        got = np.array([L.oracle_time_to_cycles(int(p), f) for p in ps], np.uint64)
+        np.testing.assert_array_equal(got, to_cyc[i], err_msg="time_to_cycles at %s GHz" % f)
+    # the fixture tells ceil from truncation and from rounding to nearest
+    i15, c7 = freqs.index(1.5), int(np.flatnonzero(cyc == 7)[0])
+    assert int(to_ps[i15, c7]) == 4667
+    assert int(to_cyc[i15, int(np.flatnonzero(ps == 2001)[0])]) == 4
+
+
 @pytest.mark.parametrize("name", [k for k, v in M.items() if v["kind"] == "quartet"])
 def test_cache_quartet_reference_sequences(name):
     e = M[name]
