@@ -11,7 +11,7 @@ import os
 import numpy as np
 
 from .config import (GGConfig, NUM_CACHE_COUNTERS, NUM_NET_COUNTERS, NUM_TILE_STATS, NUM_RUN_INFO, NUM_CORE_STATS,
-                     CMSG_DTYPE)
+                     CMSG_DTYPE, AtacParams, NUM_ATAC_COUNTERS)
 
 CMSG_BYTES = CMSG_DTYPE.itemsize
 
@@ -62,7 +62,8 @@ EXPORTS = ["gg_abi_version", "gg_last_error", "gg_config_default", "gg_create", 
            "gg_split_accesses", "gg_combine_accesses", "gg_dump_summary", "gg_core_model_run", "gg_core_get_stats", "gg_coherent_get_miss_types",
            "gg_coherent_get_protocol_stats", "gg_iocoom_run", "gg_iocoom_get_stats",
            "gg_round_pack", "gg_round_unpack", "gg_round_finish", "gg_coherent_run_many",
-           "gg_stats_trace_configure", "gg_stats_trace_sample", "gg_stats_trace_get", "gg_stats_trace_dump"]
+           "gg_stats_trace_configure", "gg_stats_trace_sample", "gg_stats_trace_get", "gg_stats_trace_dump",
+           "gg_atac_params_default", "gg_noc_set_atac", "gg_atac_topology", "gg_noc_get_atac_counters"]
 
 # statistics trace (gg_stats_trace_*): GG_ST_* statistics bits, GG_STF_* sample fields
 ST_NETWORK_UTILIZATION, ST_CACHE_LINE_REPLICATION = 1, 2
@@ -156,6 +157,13 @@ def load():
     L.gg_stats_trace_get.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
     L.gg_stats_trace_dump.argtypes = [vp, i32, ctypes.c_char_p, u64, ctypes.POINTER(u64)]
     for name in ["gg_stats_trace_configure", "gg_stats_trace_sample", "gg_stats_trace_get", "gg_stats_trace_dump"]:
+        getattr(L, name).restype = i32
+    L.gg_atac_params_default.argtypes = [ctypes.POINTER(AtacParams)]
+    L.gg_atac_params_default.restype = None
+    L.gg_noc_set_atac.argtypes = [vp, ctypes.POINTER(AtacParams)]
+    L.gg_atac_topology.argtypes = [u32, ctypes.POINTER(AtacParams), vp, vp, vp, vp]
+    L.gg_noc_get_atac_counters.argtypes = [vp, vp]
+    for name in ["gg_noc_set_atac", "gg_atac_topology", "gg_noc_get_atac_counters"]:
         getattr(L, name).restype = i32
     for name in ["gg_kernel_stats", "gg_shard_map", "gg_coherent_begin", "gg_coherent_quantum", "gg_coherent_export",
                  "gg_coherent_import", "gg_coherent_run", "gg_coherent_get_stats", "gg_gen_hotspot_trace",
@@ -314,6 +322,17 @@ class Backend:
         out = np.zeros(self.cfg.num_tiles * NUM_NET_COUNTERS, np.uint64)
         _check(load().gg_noc_get_counters(self.h, out.ctypes.data_as(ctypes.c_void_p)))
         return out.reshape(self.cfg.num_tiles, NUM_NET_COUNTERS)
+
+    def noc_set_atac(self, params):
+        """gg_noc_set_atac: the ATAC settings (config.AtacParams) of a NET_ATAC
+        context; reallocates the ATAC queues and resets the NoC state."""
+        _check(load().gg_noc_set_atac(self.h, ctypes.byref(params)))
+
+    def noc_atac_counters(self):
+        """gg_noc_get_atac_counters: [tile][NUM_ATAC_COUNTERS] (config.ATAC_COUNTERS)."""
+        out = np.zeros(self.cfg.num_tiles * NUM_ATAC_COUNTERS, np.uint64)
+        _check(load().gg_noc_get_atac_counters(self.h, out.ctypes.data_as(ctypes.c_void_p)))
+        return out.reshape(self.cfg.num_tiles, NUM_ATAC_COUNTERS)
 
     # ---- coherent mode (Mode C) ----------------------------------------
     def _trace(self, addr, meta, tile_offsets):
@@ -564,6 +583,15 @@ def shard_map(num_tiles, num_shards):
     out = np.zeros(num_tiles, np.uint32)
     _check(load().gg_shard_map(num_tiles, num_shards, out.ctypes.data_as(ctypes.c_void_p)))
     return out
+
+
+def atac_topology(num_tiles, params):
+    """gg_atac_topology: (cluster_of, access_point_of, hub_of_cluster, star_index_of)."""
+    T = int(num_tiles)
+    _check(load().gg_atac_topology(T, ctypes.byref(params), None, None, None, None))   # the checks, before any buffer
+    outs = [np.zeros(n, np.uint32) for n in (T, T, T // params.cluster_size, T)]
+    _check(load().gg_atac_topology(T, ctypes.byref(params), *[o.ctypes.data_as(ctypes.c_void_p) for o in outs]))
+    return tuple(outs)
 
 
 def gen_uniform_trace(addr, meta, tile_begin, tiles, per_tile, first=0, lines_log2=15, base_shift=26, stream=None):

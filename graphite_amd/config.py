@@ -15,6 +15,12 @@ POLICY_ROUND_ROBIN = 1
 NET_MAGIC = 0
 NET_EMESH_HOP_COUNTER = 1
 NET_EMESH_HOP_BY_HOP = 2
+NET_ATAC = 3
+# network/atac (carbon_sim.cfg:318-352): receive_network_type, global_routing_strategy
+ATAC_STAR, ATAC_BTREE = 0, 1
+ATAC_CLUSTER_BASED, ATAC_DISTANCE_BASED = 0, 1
+ATAC_LASER_UNICAST, ATAC_LASER_BROADCAST = 1, 2
+ATAC_MAX_STAR_PORTS = 16      # GG_ATAC_MAX_STAR_PORTS: largest cluster_size the star stage holds
 # queue model types (QueueModel::create, queue_model.cc:19-39) and queue_model/basic moving averages
 QM_HISTORY_TREE = 0
 QM_HISTORY_LIST = 1
@@ -60,6 +66,13 @@ NET_COUNTERS = ["packets_sent", "flits_sent", "bits_sent", "packets_received",
                ["packets_broadcasted", "flits_broadcasted", "bits_broadcasted"] + \
                ["crossbar%d" % m for m in range(2, 6)]
 BROADCAST = 0xDEADBABE   # NetPacket::BROADCAST (network.h:54), GG_BROADCAST
+# gg_noc_get_atac_counters, [tile][NUM_ATAC_COUNTERS] (GG_AC_*): RouterModel event / contention
+# counters (router_model.cc:119-144) per router class, then the link counters
+ATAC_COUNTERS = ["%s_%s" % (r, c) for r in ("enet", "send_hub", "receive_hub", "star_net")
+                 for c in ("buffer_writes", "switch_alloc", "crossbar_one", "crossbar_all",
+                           "contention_cycles", "port_packets")] + \
+                ["enet_link_flits", "optical_unicast_flits", "optical_broadcast_flits", "receive_net_link_flits"]
+NUM_ATAC_COUNTERS = len(ATAC_COUNTERS)
 NUM_CACHE_COUNTERS = len(CACHE_COUNTERS)
 
 # coherent mode (include/graphite_gpu.h)
@@ -118,6 +131,22 @@ class IocoomParams(ctypes.Structure):
 
     def __init__(self, lq=8, sq=8, spec=1, rfo=1):
         super().__init__(lq, sq, spec, rfo)
+
+
+class AtacParams(ctypes.Structure):
+    """gg_atac_params; defaults = carbon_sim.cfg [network/atac] (:318-352) and
+    [link_model/optical] laser_modes (:366-370)."""
+    _fields_ = [(n, ctypes.c_uint32) for n in (
+        "cluster_size", "num_access_points", "receive_net_type", "num_receive_nets", "global_routing",
+        "unicast_distance_threshold", "enet_router_delay", "send_hub_router_delay", "receive_hub_router_delay",
+        "star_net_router_delay", "laser_modes")]
+
+    def __init__(self, **kw):
+        super().__init__(4, 4, ATAC_STAR, 2, ATAC_CLUSTER_BASED, 4, 1, 1, 1, 1, 3)
+        for k, v in kw.items():
+            if not hasattr(self, k):
+                raise KeyError(k)
+            setattr(self, k, v)
 
 
 CMSG_DTYPE = None  # filled below (numpy view of gg_cmsg)
@@ -273,3 +302,65 @@ def shard_map(num_tiles, num_shards):
 def shard_of_tile(tile, num_tiles, num_shards):
     """Logical shard of a tile (shard_map)."""
     return int(shard_map(num_tiles, num_shards)[tile])
+
+
+def _isqrt_exact(n):
+    r = math.isqrt(n)
+    return r if r * r == n else None
+
+
+def atac_check(num_tiles, params):
+    """The checks of NetworkModelAtac::initializeANetTopologyParams
+    (network_model_atac.cc:104-121); raises ValueError naming the field."""
+    T, cs, ap = int(num_tiles), int(params.cluster_size), int(params.num_access_points)
+    p2 = lambda n: n > 0 and n & (n - 1) == 0
+    if not p2(T) or _isqrt_exact(T) is None:
+        raise ValueError("num_tiles %d must be a power of two and a perfect square" % T)
+    if not p2(cs):
+        raise ValueError("cluster_size %d must be a power of two" % cs)
+    if not p2(ap):
+        raise ValueError("num_access_points %d must be a power of two" % ap)
+    if ap > cs:
+        raise ValueError("num_access_points %d above cluster_size %d" % (ap, cs))
+    if T % cs or T // cs < 2:
+        raise ValueError("cluster_size %d leaves fewer than 2 clusters of %d tiles" % (cs, T))
+    if params.num_receive_nets == 0:
+        raise ValueError("num_receive_nets must be at least 1")
+    if params.laser_modes == 0 or params.laser_modes > 3:
+        raise ValueError("laser_modes must enable unicast (1), broadcast (2) or both")
+
+
+def atac_topology(num_tiles, params):
+    """(cluster_of[T], access_point_of[T], hub_of_cluster[C], star_index_of[T]) of
+    the ATAC network (NetworkModelAtac::initializeClusters, getClusterID,
+    getNearestAccessPoint, getTileIDWithOpticalHub, getTileIDListInCluster:
+    network_model_atac.cc:587-745).  Same rule as the ABI's gg_atac_topology."""
+    atac_check(num_tiles, params)
+    T, cs, nap = int(num_tiles), int(params.cluster_size), int(params.num_access_points)
+    W = math.isqrt(T)
+    C = T // cs
+
+    def grid(n, wide):
+        # even log2: square; odd: X = sqrt(n/2), Y = sqrt(2n) for clusters (:594-603),
+        # the other way round for sub-clusters (:621-630)
+        if (n.bit_length() - 1) % 2 == 0:
+            return math.isqrt(n), math.isqrt(n)
+        a, b = math.isqrt(n // 2), math.isqrt(n * 2)
+        return (b, a) if wide else (a, b)
+
+    nx, ny = grid(C, False)
+    cw, ch = W // nx, W // ny
+    sx, sy = grid(nap, True)
+    sw, sh = cw // sx, ch // sy
+    if sw == 0 or sh == 0:
+        raise ValueError("num_access_points %d does not tile a %d x %d cluster" % (nap, cw, ch))
+    cmw = W // cw
+    t = np.arange(T)
+    x, y = t % W, t // W
+    cluster = (y // ch) * cmw + x // cw
+    minx, miny = (cluster % cmw) * cw, (cluster // cmw) * ch
+    ap = (miny + ((y - miny) // sh) * sh + sh // 2) * W + minx + ((x - minx) // sw) * sw + sw // 2
+    c = np.arange(C)
+    hub = ((c // cmw) * ch + ch // 2) * W + (c % cmw) * cw + cw // 2
+    star = (x - minx) * ch + (y - miny)
+    return cluster.astype(np.uint32), ap.astype(np.uint32), hub.astype(np.uint32), star.astype(np.uint32)

@@ -399,6 +399,7 @@ void gg_coh_free(gg_ctx* ctx)
 
 static gg_status coh_alloc(gg_ctx* ctx)
 {
+  GG_NOT_ATAC(ctx, "coherent mode");
   if (ctx->coh) return GG_OK;
   const gg_config& c = ctx->cfg;
   gg_coh_state* C = new gg_coh_state();
@@ -709,6 +710,7 @@ gg_status gg_coh_launch_state(gg_ctx* ctx, const CP** P, const CS** S, bool* beg
 
 gg_status gg_coherent_begin(gg_ctx* ctx, const gg_trace* tr, uint64_t* access_out_dev, void* stream)
 {
+  GG_NOT_ATAC(ctx, "gg_coherent_begin");
   if (!ctx || !tr || !tr->tile_offsets) return gg_fail(GG_ERR_INVALID, "NULL argument");
   hipSetDevice(ctx->device);
   hipStream_t s = (hipStream_t)stream;
@@ -818,6 +820,7 @@ static gg_status coh_quantum_steps(gg_ctx* ctx, uint64_t q)
 
 gg_status gg_coherent_quantum(gg_ctx* ctx, uint64_t q, gg_coherent_status* out)
 {
+  GG_NOT_ATAC(ctx, "gg_coherent_quantum");
   if (!ctx || !out) return gg_fail(GG_ERR_INVALID, "NULL argument");
   gg_coh_state* C = ctx->coh;
   if (!C || !C->begun) return gg_fail(GG_ERR_INVALID, "gg_coherent_begin first");
@@ -908,6 +911,7 @@ uint64_t gg_coh_generation(gg_ctx* ctx) { return ctx->coh ? ctx->coh->gen : 0; }
 
 gg_status gg_coherent_export(gg_ctx* ctx, gg_cmsg* out_dev, uint64_t cap, uint64_t* per_shard_counts)
 {
+  GG_NOT_ATAC(ctx, "gg_coherent_export");
   if (!ctx || !per_shard_counts) return gg_fail(GG_ERR_INVALID, "NULL argument");
   gg_coh_state* C = ctx->coh;
   if (!C || !C->begun) return gg_fail(GG_ERR_INVALID, "gg_coherent_begin first");
@@ -941,6 +945,7 @@ gg_status gg_coherent_export(gg_ctx* ctx, gg_cmsg* out_dev, uint64_t cap, uint64
 
 gg_status gg_coherent_import(gg_ctx* ctx, const gg_cmsg* in_dev, uint64_t n)
 {
+  GG_NOT_ATAC(ctx, "gg_coherent_import");
   if (!ctx) return gg_fail(GG_ERR_INVALID, "NULL argument");
   gg_coh_state* C = ctx->coh;
   if (!C || !C->begun) return gg_fail(GG_ERR_INVALID, "gg_coherent_begin first");
@@ -960,6 +965,7 @@ gg_status gg_coherent_import(gg_ctx* ctx, const gg_cmsg* in_dev, uint64_t n)
 
 gg_status gg_coherent_run(gg_ctx* ctx, const gg_trace* tr, uint64_t* access_out_dev, void* stream)
 {
+  GG_NOT_ATAC(ctx, "gg_coherent_run");
   if (!ctx) return gg_fail(GG_ERR_INVALID, "NULL argument");
   const gg_config& c = ctx->cfg;
   const uint32_t K = c.num_shards ? c.num_shards : 1;
@@ -1153,6 +1159,7 @@ gg_status gg_coherent_run_many(gg_ctx* const* ctxs, uint32_t n, const gg_trace* 
       if (seen[i].first == seen[i - 1].first && seen[i].second < dup) { dup = seen[i].second; of = seen[i - 1].second; }
     if (dup != ~0u) return gg_fail(GG_ERR_INVALID, "gg_coherent_run_many: context %u is context %u again", dup, of);
   }
+  for (uint32_t i = 0; i < n; ++i) GG_NOT_ATAC(ctxs[i], "gg_coherent_run_many");
   for (uint32_t i = 0; i < n; ++i) {
     const gg_config& c = ctxs[i]->cfg;
     const uint32_t K = c.num_shards ? c.num_shards : 1;

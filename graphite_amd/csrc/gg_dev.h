@@ -820,6 +820,18 @@ __device__ __forceinline__ uint64_t route_closed_form(const NocParams& P, uint32
 
 }  // namespace gg
 
+// ATAC (gg_noc_atac.hip): its state hangs off the context (gg_ctx::atac)
+gg_status gg_atac_alloc(gg_ctx* ctx, const gg_atac_params* p);   // NULL: the defaults
+void      gg_atac_free(gg_ctx* ctx);
+gg_status gg_atac_reset(gg_ctx* ctx, hipStream_t s);
+gg_status gg_atac_run(gg_ctx* ctx, const gg_packets* pk, const gg_packet_out* out, const gg_packet_out* bout,
+                      uint64_t nb, hipStream_t s);
+// the mesh stage pipeline as ATAC's ENet (gg_noc.hip: noc_hbh_stages), and the
+// per-packet time / zero-load / contention arrays it leaves
+gg_status gg_noc_enet_stages(gg_ctx* ctx, const uint32_t* src, const uint32_t* dst_inj, const uint32_t* dst_xy,
+                             const uint32_t* dst_self, const uint32_t* len, const uint64_t* t0, uint64_t n, hipStream_t s);
+void gg_noc_packet_state(gg_ctx* ctx, uint64_t** t, uint64_t** zl, uint64_t** ct);
+void gg_noc_set_enet(gg_ctx* ctx, uint32_t router_delay);
 // accessors of the NoC state (gg_noc.hip) for the coherent path
 gg::NocParams gg_noc_params(gg_ctx* ctx);
 uint64_t* gg_noc_ctr(gg_ctx* ctx);

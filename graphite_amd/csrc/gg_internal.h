@@ -70,6 +70,7 @@ struct gg_timer {
 struct gg_noc_state;
 struct gg_coh_state;
 struct gg_stats_state;
+struct gg_atac_state;
 
 struct gg_ctx {
   gg_config cfg;
@@ -99,6 +100,7 @@ struct gg_ctx {
   std::vector<uint64_t> h_chunk_start;
   // NoC
   gg_noc_state* noc = nullptr;
+  gg_atac_state* atac = nullptr;  // net_model GG_NET_ATAC (gg_noc_atac.hip)
   // coherent mode (gg_coherent.hip), allocated on first use
   gg_coh_state* coh = nullptr;
   // replay kernel choice: 0 = lean when instantiated (default), 1 = generic
@@ -130,6 +132,12 @@ inline void gg_round_state_set(gg_ctx* ctx, void* p, void (*f)(void*)) { ctx->ro
 gg_status gg_fail(gg_status code, const char* fmt, ...);
 gg_status gg_hip_check(hipError_t e, const char* what);
 #define GG_HIP(x) do { hipError_t _e = (x); if (_e != hipSuccess) return gg_hip_check(_e, #x); } while (0)
+
+// ATAC (GG_NET_ATAC) is built for the NoC batch API only: the coherent entry points refuse such a context
+#define GG_NOT_ATAC(ctx, what) \
+  do { if ((ctx) && (ctx)->cfg.net_model == GG_NET_ATAC) \
+         return gg_fail(GG_ERR_UNSUPPORTED, "%s: the ATAC network model is built for the NoC batch API only " \
+                        "(gg_noc_route_batch / gg_noc_route_tree)", what); } while (0)
 
 // timing helpers (gg_capi.hip)
 void gg_timer_begin(gg_ctx* ctx, const char* name, hipStream_t s);

@@ -14,6 +14,7 @@
 // chain with a private (time, index) event heap, which reproduces the order of
 // one global event queue exactly.
 #include "gg_dev.h"
+#include "gg_noc_stage.h"
 
 #include <hip/hip_cooperative_groups.h>
 
@@ -443,40 +444,9 @@ __device__ void chain_staged(NocDev D, int stage, const uint32_t* __restrict__ d
 // <= kSweepPk packets, <= kSweepPos positions, history_tree queues of <=
 // kQMaxNoc intervals (or no queue model), flits < 2^16.
 // ---------------------------------------------------------------------------
-constexpr uint32_t kSweepPk = 6144, kSweepSort = 8192, kSweepPos = 256, kSweepThreads = 256, kQMaxNoc = 128;
-struct SK { uint64_t t; uint32_t i, pad; };
-static_assert(sizeof(SK) == 16 && sizeof(Ev) >= 2 * sizeof(SK), "start runs + arrivals fit a bucket's Ev scratch");
+constexpr uint32_t kSweepPk = 6144, kSweepSort = 8192, kSweepPos = 256, kSweepThreads = 256;
+static_assert(sizeof(Ev) >= 2 * sizeof(SK), "start runs + arrivals fit a bucket's Ev scratch");
 constexpr size_t kSweepLds = (size_t)kSweepSort * sizeof(SK) + (size_t)kSweepPk * 4 + kSweepPos * 8 + 64;
-__device__ __forceinline__ bool sk_lt(const SK& a, const SK& b) { return a.t < b.t || (a.t == b.t && a.i < b.i); }
-__device__ __forceinline__ void nsync()   // LDS ordering between the lanes of one wave of a multi-wave workgroup
-{
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-__device__ __forceinline__ uint64_t wave_sum64n(uint64_t v)
-{
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (uint64_t)__shfl_xor((long long)v, o);
-  return v;
-}
-
-// ascending bitonic sort of a[0, M), M a power of two, all threads of the block
-template <class T, class Lt>
-__device__ void block_bitonic(T* a, uint32_t M, Lt lt)
-{
-  for (uint32_t k = 2; k <= M; k <<= 1)
-    for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-      for (uint32_t i = threadIdx.x; i < M; i += blockDim.x) {
-        const uint32_t l = i ^ j;
-        if (l > i) {
-          const T x = a[i], y = a[l];
-          if (((i & k) == 0) == lt(y, x)) { a[i] = y; a[l] = x; }
-        }
-      }
-      __syncthreads();
-    }
-}
 
 __device__ void chain_sweep(NocDev D, int stage, const uint32_t* __restrict__ dst,
     const uint32_t* __restrict__ len, const uint64_t* __restrict__ bucket_off, uint32_t* __restrict__ bucket_ids,
@@ -640,7 +610,10 @@ __global__ __launch_bounds__(kSweepThreads) void k_chain_sweep(NocDev D, int sta
 // unchanged.  Chains beyond the limits take the position sweep.
 // ---------------------------------------------------------------------------
 constexpr uint32_t kPipePos = 32, kPipeK = 2, kPipeWaves = kPipePos / kPipeK, kPipeBatch = 256, kPipePk = 6144;
-constexpr size_t kPipeLds = (size_t)kPipeWaves * kPipeBatch * sizeof(SK) + (size_t)kPipePk * 4 + 3 * kPipePos * 4 + 64;
+// ATAC's ENet gathers a cluster's optical traffic in the access points' columns, twice the packets a mesh
+// chain sees: its chains take the pipeline up to kPipePkEnet packets (pk_max below; the mesh keeps kPipePk)
+constexpr uint32_t kPipePkEnet = kPipeWaves * kPipeBatch * 4;
+constexpr size_t kPipeLds = (size_t)kPipeWaves * kPipeBatch * sizeof(SK) + (size_t)kPipePkEnet * 4 + 3 * kPipePos * 4 + 64;
 static_assert(kPipeLds <= kStageLdsMax, "pipeline LDS");
 
 // one position of a pipelined chain, held by a wave across the slabs
@@ -653,7 +626,7 @@ __device__ __forceinline__ bool sk_below(const SK& x, uint64_t bt, uint32_t bi) 
 
 __global__ __launch_bounds__(64 * kPipeWaves) void k_chain_pipe(NocDev D, int stage, const uint32_t* __restrict__ dst,
     const uint32_t* __restrict__ len, const uint64_t* __restrict__ bucket_off, uint32_t* __restrict__ bucket_ids,
-    Ev* heap, PktState S, SK* pscr, uint64_t pstride, unsigned long long* prof)
+    Ev* heap, PktState S, SK* pscr, uint64_t pstride, uint32_t pk_max, unsigned long long* prof)
 {
   if (!GG_NOC_DIAG) prof = nullptr;
   extern __shared__ __attribute__((aligned(16))) uint8_t qlds[];
@@ -663,14 +636,14 @@ __global__ __launch_bounds__(64 * kPipeWaves) void k_chain_pipe(NocDev D, int st
   if (b == e) return;
   const uint32_t npos = stage == 0 ? P.w : P.h;
   const bool regq = P.qtype == GG_QM_HISTORY_TREE && P.max_size <= kQMaxNoc;
-  if (e - b > kPipePk || npos > kPipePos || (P.qm && !regq)) {
+  if (e - b > pk_max || npos > kPipePos || (P.qm && !regq)) {
     chain_sweep(D, stage, dst, len, bucket_off, bucket_ids, heap, S, prof, c);
     return;
   }
   const uint32_t n = (uint32_t)(e - b);
   SK* A = reinterpret_cast<SK*>(qlds);                                         // [waves][kPipeBatch] slab batches
   uint32_t* info = reinterpret_cast<uint32_t*>(A + (size_t)kPipeWaves * kPipeBatch);   // [n] flits | exit position << 16
-  uint32_t* npool = info + kPipePk;                                            // [npos] pool counts
+  uint32_t* npool = info + pk_max;                                             // [npos] pool counts
   uint32_t* ninc = npool + kPipePos;                                           // [2][npos] incoming counts
   __shared__ uint32_t s_bad, s_left;
   __shared__ uint64_t s_tmin, s_tmax;
@@ -689,7 +662,7 @@ __global__ __launch_bounds__(64 * kPipeWaves) void k_chain_pipe(NocDev D, int st
   // 1. the chain's ids in index order (i = rank by index), info, start pools
   uint32_t M = 1;
   while (M < n) M <<= 1;
-  uint32_t* ia = reinterpret_cast<uint32_t*>(A);                               // n <= kPipePk <= waves * batch * 4
+  uint32_t* ia = reinterpret_cast<uint32_t*>(A);                               // n <= pk_max <= waves * batch * 4
   for (uint32_t i = tid; i < M; i += blockDim.x) ia[i] = i < n ? ids[i] : 0xFFFFFFFFu;
   __syncthreads();
   block_bitonic(ia, M, [](uint32_t x, uint32_t y) { return x < y; });
@@ -984,7 +957,6 @@ __global__ __launch_bounds__(64 * kPortWaves) void k_port_sweep(NocDev D, const 
 }
 
 // bucket keys: 0 = injection (src tile), 1 = X chain, 2 = Y chain, 3 = SELF (dst tile); ~0 = not in stage
-__device__ __forceinline__ uint64_t batch_n(uint64_t n, const uint32_t* n_dev) { return n_dev ? min((uint64_t)*n_dev, n) : n; }
 
 __global__ void k_keys(NocParams P, int stage, const uint32_t* __restrict__ src, const uint32_t* __restrict__ dst,
                        uint64_t cap, const uint32_t* n_dev, uint32_t* keys, uint32_t* counts, uint32_t* err)
@@ -1005,31 +977,6 @@ __global__ void k_keys(NocParams P, int stage, const uint32_t* __restrict__ src,
   if (key != ~0u) atomicAdd(&counts[key], 1u);
 }
 
-__global__ void k_scan_counts(const uint32_t* counts, uint32_t nb, uint64_t* off, uint32_t* cursor)
-{
-  // single block; nb is small (<= 2 * 4096)
-  __shared__ uint64_t part[1024];
-  const uint32_t t = threadIdx.x, per = (nb + blockDim.x - 1) / blockDim.x;
-  uint64_t s = 0;
-  for (uint32_t i = t * per; i < min(nb, (t + 1) * per); ++i) s += counts[i];
-  part[t] = s;
-  __syncthreads();
-  if (t == 0) { uint64_t a = 0; for (uint32_t i = 0; i < blockDim.x; ++i) { uint64_t v = part[i]; part[i] = a; a += v; } off[nb] = a; }
-  __syncthreads();
-  uint64_t a = part[t];
-  for (uint32_t i = t * per; i < min(nb, (t + 1) * per); ++i) { off[i] = a; cursor[i] = 0; a += counts[i]; }
-}
-
-__global__ void k_bucket(const uint32_t* __restrict__ keys, uint64_t cap, const uint32_t* n_dev,
-                         const uint64_t* __restrict__ off, uint32_t* cursor, uint32_t* ids)
-{
-  const uint64_t n = batch_n(cap, n_dev);
-  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= n) return;
-  const uint32_t key = keys[k];
-  if (key == ~0u) return;
-  ids[off[key] + atomicAdd(&cursor[key], 1u)] = (uint32_t)k;
-}
 
 __global__ void k_init_pkts(const uint32_t* __restrict__ src, const uint64_t* __restrict__ t0, uint64_t cap,
                             const uint32_t* n_dev, PktState S)
@@ -2112,12 +2059,14 @@ gg_status gg_noc_alloc(gg_ctx* ctx)
   S->nq = (uint64_t)c.num_tiles * 6 + 1;
   GG_HIP(hipMalloc((void**)&S->q, sizeof(HQueue) * S->nq));
   GG_HIP(hipMalloc((void**)&S->nd, sizeof(HNode) * S->nq * P.max_size));
+  if (c.net_model == GG_NET_ATAC) return gg_atac_alloc(ctx, nullptr);
   return GG_OK;
 }
 
 void gg_noc_free(gg_ctx* ctx)
 {
   gg_noc_state* S = ctx->noc;
+  gg_atac_free(ctx);
   if (!S) return;
   void* ps[] = {S->q, S->nd, S->ctr, S->t, S->zl, S->ct, S->cur, S->keys, S->ids, S->heap,
                 S->counts, S->cursor, S->off, S->theap, S->bidx, S->prof, S->pscr, S->tp, S->tg};
@@ -2133,6 +2082,7 @@ gg_status gg_noc_reset(gg_ctx* ctx, hipStream_t s)
   hipLaunchKernelGGL(k_htree_reset, dim3((uint32_t)((S->nq + 255) / 256)), dim3(256), 0, s, S->q, S->nd,
                      S->nq, S->P.max_size, S->P.qtype, S->P.qaux);
   GG_HIP(hipGetLastError());
+  if (S->P.net_model == GG_NET_ATAC) return gg_atac_reset(ctx, s);
   return GG_OK;
 }
 
@@ -2178,6 +2128,7 @@ gg_status gg_noc_run(gg_ctx* ctx, const gg_packets* pk, const gg_packet_out* out
     gg_timer_end(ctx, "noc_hop_counter", s);
     return GG_OK;
   }
+  if (P.net_model == GG_NET_ATAC) return gg_atac_run(ctx, pk, out, nullptr, 0, s);
   if (P.net_model != GG_NET_EMESH_HOP_BY_HOP) return gg_fail(GG_ERR_UNSUPPORTED, "network model %u", P.net_model);
   if (P.w * P.h != P.tiles) return gg_fail(GG_ERR_UNSUPPORTED, "emesh_hop_by_hop needs a full W x H mesh (hop_by_hop.cc:55-59)");
   if (gg_status st = gg_noc_hbh(ctx, pk->src_dev, pk->dst_dev, pk->length_bits_dev, pk->time_ps_dev, nullptr, nullptr,
@@ -2195,6 +2146,10 @@ gg_status gg_noc_tree(gg_ctx* ctx, const gg_packets* pk, const gg_packet_out* ou
   gg_noc_state* S = ctx->noc;
   const NocParams& P = S->P;
   const uint64_t n = pk->num_packets;
+  if (P.net_model == GG_NET_ATAC) {
+    if (nb && !bout) return gg_fail(GG_ERR_INVALID, "NULL packet or output pointer");
+    return gg_atac_run(ctx, pk, out, bout, nb, s);
+  }
   if (P.net_model != GG_NET_EMESH_HOP_BY_HOP)
     return gg_fail(GG_ERR_UNSUPPORTED, "broadcast tree: emesh_hop_by_hop only (network.cc:187-195 unrolls the others)");
   if (P.w * P.h != P.tiles) return gg_fail(GG_ERR_UNSUPPORTED, "emesh_hop_by_hop needs a full W x H mesh (hop_by_hop.cc:55-59)");
@@ -2328,12 +2283,37 @@ gg_status gg_noc_tree(gg_ctx* ctx, const gg_packets* pk, const gg_packet_out* ou
 // `cap` or, when n_dev is given, *n_dev read on the device (the coherent path
 // launches whole batches of steps without a host sync).  Arrival / zero-load /
 // contention land in the NoC state's packet arrays (gg_noc_packet_times).
+// dst_inj / dst_xy / dst_self: the destination the injection stage, the X and
+// Y chains and the SELF stage see.  The mesh passes the receiver three times;
+// ATAC (gg_noc_atac.hip) routes its ENet part here: the chains run to the
+// packet's ENet target (the receiver, or the sender's access point) and the
+// packets that go on to the optical network are masked out of the SELF stage
+// (dst_self = src: a stage skips packets whose source is its destination).
+static gg_status noc_hbh_stages(gg_ctx* ctx, const uint32_t* src, const uint32_t* dst_inj, const uint32_t* dst_xy,
+                                const uint32_t* dst_self, const uint32_t* len, const uint64_t* t0, const uint64_t* khi,
+                                const uint64_t* klo, uint64_t cap, const uint32_t* n_dev, hipStream_t s);
+
 gg_status gg_noc_hbh(gg_ctx* ctx, const uint32_t* src, const uint32_t* dst, const uint32_t* len, const uint64_t* t0,
                      const uint64_t* khi, const uint64_t* klo, uint64_t cap, const uint32_t* n_dev, hipStream_t s)
 {
+  if (ctx->noc->P.net_model != GG_NET_EMESH_HOP_BY_HOP)
+    return gg_fail(GG_ERR_UNSUPPORTED, "network model %u", ctx->noc->P.net_model);
+  return noc_hbh_stages(ctx, src, dst, dst, dst, len, t0, khi, klo, cap, n_dev, s);
+}
+
+gg_status gg_noc_enet_stages(gg_ctx* ctx, const uint32_t* src, const uint32_t* dst_inj, const uint32_t* dst_xy,
+                             const uint32_t* dst_self, const uint32_t* len, const uint64_t* t0, uint64_t n, hipStream_t s)
+{
+  if (ctx->noc->P.net_model != GG_NET_ATAC) return gg_fail(GG_ERR_INVALID, "not an ATAC context");
+  return noc_hbh_stages(ctx, src, dst_inj, dst_xy, dst_self, len, t0, nullptr, nullptr, n, nullptr, s);
+}
+
+static gg_status noc_hbh_stages(gg_ctx* ctx, const uint32_t* src, const uint32_t* dst_inj, const uint32_t* dst_xy,
+                                const uint32_t* dst_self, const uint32_t* len, const uint64_t* t0, const uint64_t* khi,
+                                const uint64_t* klo, uint64_t cap, const uint32_t* n_dev, hipStream_t s)
+{
   gg_noc_state* S = ctx->noc;
   const NocParams& P = S->P;
-  if (P.net_model != GG_NET_EMESH_HOP_BY_HOP) return gg_fail(GG_ERR_UNSUPPORTED, "network model %u", P.net_model);
   if (P.w * P.h != P.tiles) return gg_fail(GG_ERR_UNSUPPORTED, "emesh_hop_by_hop needs a full W x H mesh (hop_by_hop.cc:55-59)");
   if (cap >= (1ull << 32)) return gg_fail(GG_ERR_RANGE, "batch larger than 2^32 packets");
   const uint32_t nb_max = std::max(P.tiles, 2 * std::max(P.w, P.h));
@@ -2345,6 +2325,7 @@ gg_status gg_noc_hbh(gg_ctx* ctx, const uint32_t* src, const uint32_t* dst, cons
   hipLaunchKernelGGL(k_init_pkts, dim3(blocks), dim3(256), 0, s, src, t0, cap, n_dev, PS);
   for (int stage = 0; stage < 4; ++stage) {
     const uint32_t nb = (stage == 0 || stage == 3) ? P.tiles : (stage == 1 ? 2 * P.h : 2 * P.w);
+    const uint32_t* dst = stage == 0 ? dst_inj : stage == 3 ? dst_self : dst_xy;
     GG_HIP(hipMemsetAsync(S->counts, 0, 4 * (nb + 1), s));
     hipLaunchKernelGGL(k_keys, dim3(blocks), dim3(256), 0, s, P, stage, src, dst, cap, n_dev, S->keys,
                        S->counts, ctx->err_dev);
@@ -2373,7 +2354,7 @@ gg_status gg_noc_hbh(gg_ctx* ctx, const uint32_t* src, const uint32_t* dst, cons
         S->pscr_cap = cap * stride;
       }
       hipLaunchKernelGGL(k_chain_pipe, dim3(nb), dim3(64 * kPipeWaves), kStageLdsMax, s, D, stage - 1, dst, len, S->off,
-                         S->ids, S->heap, PS, S->pscr, stride, S->prof);
+                         S->ids, S->heap, PS, S->pscr, stride, P.net_model == GG_NET_ATAC ? kPipePkEnet : kPipePk, S->prof);
     } else if (staged) {
       hipLaunchKernelGGL(k_chain_sweep, dim3(nb), dim3(kSweepThreads), kStageLdsMax, s, D, stage - 1, dst, len, S->off,
                          S->ids, S->heap, PS, S->prof);
@@ -2408,6 +2389,10 @@ gg_status gg_noc_counters(gg_ctx* ctx, uint64_t* out)
     GG_HIP(hipStreamSynchronize(ctx->last_stream));
   }
   GG_HIP(hipMemcpy(out, S->ctr, sizeof(uint64_t) * S->P.tiles * GG_NUM_NET_COUNTERS, hipMemcpyDeviceToHost));
+  if (S->P.net_model == GG_NET_ATAC)       // the ENet router's counters are reported by gg_noc_get_atac_counters
+    for (uint32_t t = 0; t < S->P.tiles; ++t)
+      for (int k = GG_NC_BUFFER_WRITES; k < GG_NUM_NET_COUNTERS; ++k)
+        if (k < GG_NC_PACKETS_BROADCASTED || k > GG_NC_BITS_BROADCASTED) out[(size_t)t * GG_NUM_NET_COUNTERS + k] = 0;
   return GG_OK;
 }
 
@@ -2434,3 +2419,9 @@ gg_status gg_htree_run(gg_ctx* ctx, uint64_t min_proc, const uint64_t* t, const 
 gg::NocParams gg_noc_params(gg_ctx* ctx) { return ctx->noc->P; }
 void gg_noc_queues(gg_ctx* ctx, gg::HQueue** q, gg::HNode** nd) { *q = ctx->noc->q; *nd = ctx->noc->nd; }
 uint64_t* gg_noc_ctr(gg_ctx* ctx) { return ctx->noc->ctr; }
+void gg_noc_packet_state(gg_ctx* ctx, uint64_t** t, uint64_t** zl, uint64_t** ct)
+{
+  *t = ctx->noc->t; *zl = ctx->noc->zl; *ct = ctx->noc->ct;
+}
+// ATAC: the mesh stages are the ENet (its router delay; the ENet link is 1 cycle)
+void gg_noc_set_enet(gg_ctx* ctx, uint32_t router_delay) { ctx->noc->P.router_delay = router_delay; ctx->noc->P.link_delay = 1; }

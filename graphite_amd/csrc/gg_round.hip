@@ -262,11 +262,13 @@ gg_status round_decide(gg_ctx* ctx, RoundBufs* B, gg_round_io* io)
 
 gg_status gg_round_pack(gg_ctx* ctx, uint32_t world, uint32_t rank, uint64_t q, gg_round_io* io)
 {
+  GG_NOT_ATAC(ctx, "gg_round_pack");
   return round_pack(ctx, world, rank, q, io, GG_OK, "");
 }
 
 gg_status gg_round_unpack(gg_ctx* ctx, gg_round_io* io)
 {
+  GG_NOT_ATAC(ctx, "gg_round_unpack");
   if (!ctx || !io) return gg_fail(GG_ERR_INVALID, "NULL argument");
   RoundBufs* B = bufs_of(ctx);
   if (!B || !ctx->coh) return gg_fail(GG_ERR_INVALID, "gg_round_pack first");
@@ -323,6 +325,7 @@ gg_status gg_round_unpack(gg_ctx* ctx, gg_round_io* io)
 
 gg_status gg_round_finish(gg_ctx* ctx, gg_round_io* io)
 {
+  GG_NOT_ATAC(ctx, "gg_round_finish");
   if (!ctx || !io) return gg_fail(GG_ERR_INVALID, "NULL argument");
   RoundBufs* B = bufs_of(ctx);
   if (!B || !ctx->coh) return gg_fail(GG_ERR_INVALID, "gg_round_pack first");
@@ -344,6 +347,7 @@ gg_status gg_round_finish(gg_ctx* ctx, gg_round_io* io)
 
 gg_status gg_round_exchange(gg_ctx* ctx, void* nccl_comm, void* stream, uint64_t q, uint64_t* next_q, int* done)
 {
+  GG_NOT_ATAC(ctx, "gg_round_exchange");
   if (!ctx || !nccl_comm || !next_q || !done) return gg_fail(GG_ERR_INVALID, "NULL argument");
   ncclComm_t comm = static_cast<ncclComm_t>(nccl_comm);
   int W = 0, R = 0;
@@ -399,6 +403,7 @@ gg_status gg_round_exchange(gg_ctx* ctx, void* nccl_comm, void* stream, uint64_t
 
 gg_status gg_coherent_run_ranks(gg_ctx* ctx, void* nccl_comm, const gg_trace* tr, uint64_t* access_out_dev, void* stream)
 {
+  GG_NOT_ATAC(ctx, "gg_coherent_run_ranks");
   if (ctx && gg_stats_on(ctx))       // the rounds do not sample: a rank samples its shards with gg_stats_trace_sample
     return gg_fail(GG_ERR_UNSUPPORTED, "gg_coherent_run_ranks: a statistics trace is configured (drive the rounds with "
                                        "gg_round_exchange and sample with gg_stats_trace_sample)");

@@ -72,7 +72,8 @@ enum {
 enum { GG_POLICY_LRU = 0, GG_POLICY_ROUND_ROBIN = 1 };
 
 /* Network models: NetworkModel::parseNetworkType (network_model.cc:318-335) */
-enum { GG_NET_MAGIC = 0, GG_NET_EMESH_HOP_COUNTER = 1, GG_NET_EMESH_HOP_BY_HOP = 2 };
+enum { GG_NET_MAGIC = 0, GG_NET_EMESH_HOP_COUNTER = 1, GG_NET_EMESH_HOP_BY_HOP = 2,
+       GG_NET_ATAC = 3 /* batch API only: gg_noc_route_batch / gg_noc_route_tree, see gg_atac_params */ };
 
 /* Cache levels (pr_l1_pr_l2_dram_directory_msi/cache_level.h) */
 enum { GG_L1D = 0, GG_L2 = 1 };
@@ -899,6 +900,81 @@ gg_status gg_iocoom_run(gg_ctx* ctx, const gg_iocoom_params* params, const gg_in
 /* out: num_tiles * GG_NUM_IOCOOM_STATS (host).  Synchronizes.  GG_ERR_STATE
  * if gg_iocoom_run has not run on the context or its streams disagreed.    */
 gg_status gg_iocoom_get_stats(gg_ctx* ctx, uint64_t* out);
+
+/* ------------------------------------------------------------------------
+ * ATAC (network/memory = atac; models/network_model_atac.cc): an electrical
+ * mesh inside a cluster (ENet), an optical ring between the clusters' hubs
+ * (ONet) and a receive network (star or broadcast tree) per cluster.  BATCH
+ * API ONLY: gg_noc_route_batch and gg_noc_route_tree take a context whose
+ * net_model is GG_NET_ATAC; gg_coherent_*, gg_round_* and
+ * gg_coherent_run_many return GG_ERR_UNSUPPORTED on it.
+ * The settings live here, apart from gg_config (whose layout is unchanged):
+ * carbon_sim.cfg:318-352 and [link_model/optical] laser_modes (:366-370).
+ * gg_config's flit_width, queue_model_enabled, queue_model_type,
+ * max_list_size, analytical_enabled, basic_moving_avg,
+ * history_list_no_interleaving and frequency_ghz are read as the
+ * network/atac values.  Link delays are not settings: the reference asserts
+ * 1 cycle for the ENet, star and B-tree links and 3 for the optical link
+ * (network_model_atac.cc:213,229,250,281).                                  */
+enum { GG_ATAC_STAR = 0, GG_ATAC_BTREE = 1 };                       /* receive_network_type */
+enum { GG_ATAC_CLUSTER_BASED = 0, GG_ATAC_DISTANCE_BASED = 1 };     /* global_routing_strategy */
+enum { GG_ATAC_LASER_UNICAST = 1, GG_ATAC_LASER_BROADCAST = 2 };    /* laser_modes bits */
+/* The star stage serves a star router's cluster_size output ports with one
+ * wave each in one workgroup of at most 1024 threads: cluster sizes above 16
+ * are GG_ERR_UNSUPPORTED (star and B-tree alike).                           */
+#define GG_ATAC_MAX_STAR_PORTS 16u
+typedef struct gg_atac_params {
+  uint32_t cluster_size;                /* network/atac/cluster_size (4)                         */
+  uint32_t num_access_points;           /* num_optical_access_points_per_cluster (4)             */
+  uint32_t receive_net_type;            /* GG_ATAC_STAR / GG_ATAC_BTREE (star)                   */
+  uint32_t num_receive_nets;            /* num_receive_networks_per_cluster (2)                  */
+  uint32_t global_routing;              /* GG_ATAC_CLUSTER_BASED / _DISTANCE_BASED (cluster)     */
+  uint32_t unicast_distance_threshold;  /* (4)                                                   */
+  uint32_t enet_router_delay;           /* enet/router/delay (1)                                 */
+  uint32_t send_hub_router_delay;       /* onet/send_hub/router/delay (1)                        */
+  uint32_t receive_hub_router_delay;    /* onet/receive_hub/router/delay (1)                     */
+  uint32_t star_net_router_delay;       /* star_net/router/delay (1)                             */
+  uint32_t laser_modes;                 /* bit 0 unicast, bit 1 broadcast (3)                    */
+} gg_atac_params;
+void gg_atac_params_default(gg_atac_params* p);
+/* Validates p against the context's tile count (network_model_atac.cc:104-121),
+ * (re)allocates the ATAC queues and resets the NoC state (queues and
+ * counters).  A context created with net_model = GG_NET_ATAC starts with the
+ * defaults.  GG_ERR_INVALID, the message naming the field: a tile count that
+ * is not both a power of two and a perfect square, a cluster size or
+ * access-point count that is not a power of two, access points > cluster
+ * size, fewer than 2 clusters, num_receive_nets == 0, laser_modes == 0 or
+ * above 3, an unknown receive_net_type / global_routing, or a context whose
+ * model is not ATAC.  GG_ERR_UNSUPPORTED: cluster_size > GG_ATAC_MAX_STAR_PORTS. */
+gg_status gg_noc_set_atac(gg_ctx* ctx, const gg_atac_params* p);
+/* Host-only, like gg_shard_map: cluster_of[num_tiles] (getClusterID),
+ * access_point_of[num_tiles] (getNearestAccessPoint), hub_of_cluster[num_tiles
+ * / cluster_size] (getTileIDWithOpticalHub) and star_index_of[num_tiles] (the
+ * tile's index in getTileIDListInCluster: x outer, y inner), any of which may
+ * be NULL (network_model_atac.cc:587-745).  The checks of gg_noc_set_atac.   */
+gg_status gg_atac_topology(uint32_t num_tiles, const gg_atac_params* p, uint32_t* cluster_of,
+                           uint32_t* access_point_of, uint32_t* hub_of_cluster, uint32_t* star_index_of);
+/* Event and contention counters of the ATAC components a tile owns
+ * (RouterModel::updateEventCounters / updateContentionCounters,
+ * router_model.cc:119-144; ElectricalLinkModel / OpticalLinkModel flit counts,
+ * optical_link_model.cc:114-135), [tile][GG_NUM_ATAC_COUNTERS].  Per router
+ * class R = ENET, SEND_HUB, RECEIVE_HUB, STAR_NET (summed over the receive
+ * nets) at GG_AC_R + GG_ACR_*; the hub's components count on the hub's tile.
+ * The injection router is not counted (as for the mesh).                     */
+enum { GG_ACR_BUFFER_WRITES = 0, GG_ACR_SWITCH_ALLOC, GG_ACR_CROSSBAR_ONE /* flits over one output port */,
+       GG_ACR_CROSSBAR_ALL /* flits over all output ports (a router of > 1 ports) */,
+       GG_ACR_CONTENTION_CYCLES, GG_ACR_PORT_PACKETS, GG_NUM_ACR = 6 };
+enum {
+  GG_AC_ENET = 0, GG_AC_SEND_HUB = 6, GG_AC_RECEIVE_HUB = 12, GG_AC_STAR_NET = 18,
+  GG_AC_ENET_LINK_FLITS = 24, GG_AC_OPTICAL_UNICAST_FLITS, GG_AC_OPTICAL_BROADCAST_FLITS,
+  GG_AC_RECEIVE_NET_LINK_FLITS, GG_NUM_ATAC_COUNTERS
+};
+/* out: num_tiles * GG_NUM_ATAC_COUNTERS (host).  Synchronizes.  GG_ERR_INVALID
+ * on a context whose model is not ATAC.  For such a context gg_noc_get_counters
+ * fills packets / flits / bits sent and received, total latency, total
+ * contention and the three *_BROADCASTED fields; the mesh router's fields
+ * stay zero (they are here, under GG_AC_ENET).                              */
+gg_status gg_noc_get_atac_counters(gg_ctx* ctx, uint64_t* out);
 
 /* Device time (ms) of the most recent launch of a named kernel
  * ("cache_hist", "cache_scatter", "cache_replay", "cache_unshard",
