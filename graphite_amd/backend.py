@@ -63,7 +63,8 @@ EXPORTS = ["gg_abi_version", "gg_last_error", "gg_config_default", "gg_create", 
            "gg_coherent_get_protocol_stats", "gg_iocoom_run", "gg_iocoom_get_stats",
            "gg_round_pack", "gg_round_unpack", "gg_round_finish", "gg_coherent_run_many",
            "gg_stats_trace_configure", "gg_stats_trace_sample", "gg_stats_trace_get", "gg_stats_trace_dump",
-           "gg_atac_params_default", "gg_noc_set_atac", "gg_atac_topology", "gg_noc_get_atac_counters"]
+           "gg_atac_params_default", "gg_noc_set_atac", "gg_atac_topology", "gg_noc_get_atac_counters",
+           "gg_cache_track_miss_types", "gg_cache_get_miss_types"]
 
 # statistics trace (gg_stats_trace_*): GG_ST_* statistics bits, GG_STF_* sample fields
 ST_NETWORK_UTILIZATION, ST_CACHE_LINE_REPLICATION = 1, 2
@@ -164,6 +165,10 @@ def load():
     L.gg_atac_topology.argtypes = [u32, ctypes.POINTER(AtacParams), vp, vp, vp, vp]
     L.gg_noc_get_atac_counters.argtypes = [vp, vp]
     for name in ["gg_noc_set_atac", "gg_atac_topology", "gg_noc_get_atac_counters"]:
+        getattr(L, name).restype = i32
+    L.gg_cache_track_miss_types.argtypes = [vp, u32]
+    L.gg_cache_get_miss_types.argtypes = [vp, vp]
+    for name in ["gg_cache_track_miss_types", "gg_cache_get_miss_types"]:
         getattr(L, name).restype = i32
     for name in ["gg_kernel_stats", "gg_shard_map", "gg_coherent_begin", "gg_coherent_quantum", "gg_coherent_export",
                  "gg_coherent_import", "gg_coherent_run", "gg_coherent_get_stats", "gg_gen_hotspot_trace",
@@ -269,6 +274,19 @@ class Backend:
         out = np.zeros(self.cfg.num_tiles * 2 * NUM_CACHE_COUNTERS, np.uint64)
         _check(load().gg_cache_get_counters(self.h, out.ctypes.data_as(ctypes.c_void_p)))
         return out.reshape(self.cfg.num_tiles, 2, NUM_CACHE_COUNTERS)
+
+    def cache_track_miss_types(self, lines=0):
+        """gg_cache_track_miss_types: opt the context into miss-type tracking
+        for the private replay and the quartet (fresh cache state only).
+        lines: address-set capacity per (tile, cache); 0 = cfg.miss_track_lines
+        or 65536."""
+        _check(load().gg_cache_track_miss_types(self.h, lines))
+
+    def cache_miss_types(self):
+        """gg_cache_get_miss_types: [tile][L1-D, L2][cold, capacity, sharing]."""
+        out = np.zeros(self.cfg.num_tiles * 2 * 3, np.uint64)
+        _check(load().gg_cache_get_miss_types(self.h, out.ctypes.data_as(ctypes.c_void_p)))
+        return out.reshape(self.cfg.num_tiles, 2, 3)
 
     def get_line_info(self, tile, level, addr, default=None):
         li = default or LineInfo(0xFFFFFFFFFFFFFFFF, 0, 0)

@@ -17,6 +17,7 @@
 // ds_read_b32), and its records arrive through a stable per-tile partition of
 // the program-order trace (k_shard_*).
 #include "gg_internal.h"
+#include "gg_modep_mt.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -526,11 +527,20 @@ __device__ void replay_counters(const gg_cache_state& cs, const gg_geom& g, cons
   }
 }
 
-template <int A1, int A2, bool LRU1, bool LRU2>
+// Kernel argument of the miss-type tracking instances (MT = true,
+// gg_modep_mt.h).  The plain instances take the empty struct, which is no
+// kernel argument at all: with MT = false every kernel below compiles to the
+// code it had before tracking existed.
+template <bool MT> struct MtArg {};
+template <> struct MtArg<true> { gg_mt_view v; uint32_t* err; };
+
+// MT: the generic replay with miss-type tracking, for every geometry
+// gg_create accepts.
+template <int A1, int A2, bool LRU1, bool LRU2, bool MT>
 __global__ __launch_bounds__(64) void k_cache_replay(gg_cache_state cs, gg_geom g,
     const uint64_t* __restrict__ sh_key, const uint32_t* __restrict__ unit_len,
     const uint64_t* __restrict__ unit_base, uint32_t* __restrict__ sh_res,
-    uint64_t* __restrict__ sh_ev, uint32_t* err)
+    uint64_t* __restrict__ sh_ev, uint32_t* err, MtArg<MT> mta)
 {
   constexpr int MW = (A2 + 7) / 8;
   constexpr int TQ = (A2 + 3) / 4;                 // uint4 quads of tags per set
@@ -594,6 +604,13 @@ __global__ __launch_bounds__(64) void k_cache_replay(gg_cache_state cs, gg_geom 
   uint32_t cnt[NI];
 #pragma unroll
   for (int k = 0; k < NI; ++k) cnt[k] = 0;
+  gg_mt_set M1{}, M2{};
+  gg_mt_counts mc;
+  if constexpr (MT) {
+    M1 = gg_mt_set_of(mta.v, g, tile, l1set, 0);
+    M2 = gg_mt_set_of(mta.v, g, tile, l1set, 1);
+    mc.clear();
+  }
 
   // prefetch ring of the lane's record stream (distance 4)
   constexpr int PD = 4;
@@ -701,6 +718,12 @@ __global__ __launch_bounds__(64) void k_cache_replay(gg_cache_state cs, gg_geom 
     // L1-D replacement update: accessCache on the hit way or the inserted way
     if (LRU1) lru_update<1>(&m1, (uint32_t)(hit1 ? w1 : v1));
 
+    if constexpr (MT) {
+      if (!hit1)
+        gg_mt_access(M1, M2, mc, errv, line << g.log_line, w1v, miss2, upg, l2ev, e2 << g.log_line, invl1, l1ev,
+                     et << g.log_line);
+    }
+
     // -- write the L2 set back --
 #pragma unroll
     for (int w = A2; w < TQ * 4; ++w) tg[w] = GG_L2_INV_TAG;
@@ -754,6 +777,7 @@ __global__ __launch_bounds__(64) void k_cache_replay(gg_cache_state cs, gg_geom 
   }
   if (!active) errv = 0;
   if (errv) atomicOr(err, errv);
+  if constexpr (MT) { if (active) mc.flush(mta.v, tile); }
 
   replay_counters(cs, g, cnt, len, tile, lane, active);
 }
@@ -1177,10 +1201,16 @@ size_t stream_lds_bytes(uint32_t u1, uint32_t s2, uint32_t a2)
   return (size_t)s2 * u1 * (tq * 16 + (a2 > 8 ? 16 : 8)) + (size_t)kRing * u1 * 8 + (size_t)u1 * 12 + 16 + (size_t)u1 * 8 + (size_t)u1 * 4;
 }
 
-template <int A1, int A2, bool LRU1, bool LRU2, int NCW, bool EV>
+// MT: the miss-type tracking instance (kStreamMt).  The consumer's
+// step runs the table operations of gg_modep_mt.h for the lanes whose access
+// missed the L1-D, behind a wave-level "any lane missed" test: per-lane HBM
+// probes in a straight-line step, which the ring's back-pressure absorbs (the
+// producer and the hand-off are untouched).
+template <int A1, int A2, bool LRU1, bool LRU2, int NCW, bool EV, bool MT>
 __global__ __launch_bounds__((NCW + 1) * GG_WAVE) void k_cache_stream(gg_cache_state cs, gg_geom g,
     const uint64_t* __restrict__ addr, const uint32_t* __restrict__ meta, const uint64_t* __restrict__ tile_off,
-    uint32_t* __restrict__ result, uint64_t* __restrict__ evicted, uint32_t* err, unsigned long long* dbg)
+    uint32_t* __restrict__ result, uint64_t* __restrict__ evicted, uint32_t* err, unsigned long long* dbg,
+    MtArg<MT> mta)
 {
   static_assert(A1 <= 4 && (A2 <= 8 || A2 == 16), "streaming replay covers L1-D assoc <= 4, L2 assoc <= 8 or 16");
   constexpr uint32_t U1 = NCW * GG_WAVE;   // == g.u1 (host-checked)
@@ -1454,6 +1484,13 @@ __global__ __launch_bounds__((NCW + 1) * GG_WAVE) void k_cache_stream(gg_cache_s
   uint32_t* my_dummy = dummy + u;
   // 0x80 flags of a byte mask -> 0xFF bytes
   auto bytes_of = [](uint32_t m) { return m | (m - (m >> 7)); };
+  gg_mt_set M1{}, M2{};
+  gg_mt_counts mc;
+  if constexpr (MT) {
+    M1 = gg_mt_set_of(mta.v, g, tile, l1set, 0);
+    M2 = gg_mt_set_of(mta.v, g, tile, l1set, 1);
+    mc.clear();
+  }
 
   // counters: the result word's eight 1-bit nibble fields summed into byte
   // fields (even / odd nibbles), folded into u32 totals every 128 stepping
@@ -1528,7 +1565,7 @@ __global__ __launch_bounds__((NCW + 1) * GG_WAVE) void k_cache_stream(gg_cache_s
     const bool l2ev = miss2 && sv != 0;
     const bool dirty = l2ev && sv == GG_MS_M;
     uint32_t vt = 0;
-    if (EV) {
+    if (EV || MT) {
 #pragma unroll
       for (int w = 0; w < A2; ++w) vt = (w == (int)vw) ? tg[w] : vt;
     }
@@ -1567,6 +1604,26 @@ __global__ __launch_bounds__((NCW + 1) * GG_WAVE) void k_cache_stream(gg_cache_s
       l1ev = !hit1 && ((pos1 >> (8 * v1)) & 0xFFu) != 0xFFu;
     }
     v1 &= A1 - 1;
+    if constexpr (MT) {
+      // The table operations, for the lanes that missed the L1-D.  The L1-D is
+      // tagless: its victim's address is the tag of the L2 slot the victim way
+      // names (never the slot just installed or upgraded: those ways were
+      // invalidated before the victim was chosen).
+      if (__ballot(!hit1)) {
+        if (!hit1) {
+          auto addr_of = [&](uint32_t tag, uint32_t set2) {
+            return (((uint64_t)tag << log_l2) | ((uint64_t)set2 << log_u1) | l1set) << log_line;
+          };
+          uint64_t e1 = 0;
+          if (l1ev) {                                   // (an invalid way names no slot)
+            const uint32_t vs = (pos1 >> (8 * v1)) & 0xFFu, ss = vs / A2, ww = vs % A2;
+            e1 = addr_of(tag0[(ss * TQ + ww / 4) * 4 * U1 + ww % 4], ss);
+          }
+          gg_mt_access(M1, M2, mc, errv, addr_of(tag2, s), inv1 != 0, miss2, upg, l2ev, addr_of(vt, s), zbv != 0,
+                       l1ev, e1);
+        }
+      }
+    }
     {
       const uint32_t sh = 8 * v1;
       const uint32_t islot = s * A2 + (hit2 ? w2 : vw);
@@ -1697,6 +1754,7 @@ __global__ __launch_bounds__((NCW + 1) * GG_WAVE) void k_cache_stream(gg_cache_s
   cnt[I_WR] = c_wr; cnt[I_NH1] = f8[0]; cnt[I_NH1W] = c_nh1w; cnt[I_M2] = f8[1]; cnt[I_M2W] = c_m2w;
   cnt[I_W1V] = f8[2]; cnt[I_L1EV] = f8[3]; cnt[I_L2EV] = f8[4]; cnt[I_DIRTY] = f8[5]; cnt[I_INVL1] = f8[6];
   cnt[I_UPG] = f8[7];
+  if constexpr (MT) mc.flush(mta.v, tile);
   replay_counters(cs, g, cnt, h, tile, lane, true);
 }
 
@@ -1714,13 +1772,19 @@ struct QuartetIO {
   int status;
 };
 
-template <int A1, int A2>
-__global__ void k_quartet(gg_cache_state cs, gg_geom g, QuartetIO* io)
+// MT: setCacheLineInfo with an INVALID state puts the line into
+// the invalidated set (cache.cc:228-230), insertCacheLine runs the insert
+// triple (cache.cc:131-148) on the level's table (gg_modep_mt.h).
+template <int A1, int A2, bool MT>
+__global__ void k_quartet(gg_cache_state cs, gg_geom g, QuartetIO* io, MtArg<MT> mta)
 {
   constexpr int MW = (A2 + 7) / 8;
   QuartetIO q = *io;
   const uint64_t line = q.addr >> g.log_line;
   const uint64_t u = (uint64_t)q.tile * g.u1 + (line & (g.u1 - 1));
+  gg_mt_set M{};
+  uint32_t merr = 0;
+  if constexpr (MT) M = gg_mt_set_of(mta.v, g, q.tile, (uint32_t)(line & (g.u1 - 1)), q.level == GG_L1D ? 0 : 1);
   uint64_t* ctr = cs.counters + ((uint64_t)q.tile * 2 + (q.level == GG_L1D ? 0 : 1)) * NC;
   q.status = GG_OK;
   auto cstate_to_ms = [](uint32_t c, int* ok) -> uint32_t {
@@ -1750,6 +1814,7 @@ __global__ void k_quartet(gg_cache_state cs, gg_geom g, QuartetIO* io)
           meta_set_byte(&m1, wf, (meta_byte(&m1, wf) & ~7u) | ms);
           cs.l1_meta[u] = m1;
           atomicAdd((unsigned long long*)&ctr[TW], 1ull);
+          if constexpr (MT) { if (M.on() && ms == GG_MS_I) M.or_bits(line << g.log_line, gg_mt_set::kI, merr); }
         }
       }
     } else if (q.op == 2 || q.op == 3) {              // accessCacheLine
@@ -1782,6 +1847,7 @@ __global__ void k_quartet(gg_cache_state cs, gg_geom g, QuartetIO* io)
           cs.l1_meta[u] = m1;
           if (q.eviction) { ctr[TR]++; ctr[DR]++; ctr[EV]++; } else ctr[TR]++;
           ctr[TW]++; ctr[DW]++;
+          if constexpr (MT) { if (M.on()) M.insert(line << g.log_line, q.eviction != 0, q.ev_addr, merr); }
         }
       }
     }
@@ -1811,6 +1877,7 @@ __global__ void k_quartet(gg_cache_state cs, gg_geom g, QuartetIO* io)
           meta_set_byte_t<MW>(mw, wf, (meta_byte_t<MW>(mw, wf) & ~7u) | ms | (q.in.cached_loc == GG_LOC_L1D ? 4u : 0u));
           for (int k = 0; k < MW; ++k) st.set_meta(s, k, mw[k]);
           ctr[TW]++;
+          if constexpr (MT) { if (M.on() && ms == GG_MS_I) M.or_bits(line << g.log_line, gg_mt_set::kI, merr); }
         }
       }
     } else if (q.op == 2 || q.op == 3) {
@@ -1851,10 +1918,12 @@ __global__ void k_quartet(gg_cache_state cs, gg_geom g, QuartetIO* io)
           if (q.eviction) { ctr[TR]++; ctr[DR]++; ctr[EV]++; if (GG_M_STATE(vb) == GG_MS_M) ctr[DEV]++; }
           else ctr[TR]++;
           ctr[TW]++; ctr[DW]++;
+          if constexpr (MT) { if (M.on()) M.insert(line << g.log_line, q.eviction != 0, q.ev_addr, merr); }
         }
       }
     }
   }
+  if constexpr (MT) { if (merr) atomicOr(mta.err, merr); }
   *io = q;
 }
 
@@ -1862,14 +1931,19 @@ __global__ void k_quartet(gg_cache_state cs, gg_geom g, QuartetIO* io)
 // dispatch over the instantiated geometries
 // ---------------------------------------------------------------------------
 typedef void (*replay_fn)(gg_cache_state, gg_geom, const uint64_t*, const uint32_t*, const uint64_t*,
-                          uint32_t*, uint64_t*, uint32_t*);
-typedef void (*quartet_fn)(gg_cache_state, gg_geom, QuartetIO*);
+                          uint32_t*, uint64_t*, uint32_t*, MtArg<false>);
+typedef void (*quartet_fn)(gg_cache_state, gg_geom, QuartetIO*, MtArg<false>);
+// the miss-type tracking instances (an opted-in context, gg_cache_track_miss_types)
+typedef void (*replay_mt_fn)(gg_cache_state, gg_geom, const uint64_t*, const uint32_t*, const uint64_t*,
+                             uint32_t*, uint64_t*, uint32_t*, MtArg<true>);
+typedef void (*quartet_mt_fn)(gg_cache_state, gg_geom, QuartetIO*, MtArg<true>);
 
-struct Kern { int a1, a2; int lru1, lru2; replay_fn replay; quartet_fn quartet; };
+struct Kern { int a1, a2; int lru1, lru2; replay_fn replay; quartet_fn quartet; replay_mt_fn replay_mt; quartet_mt_fn quartet_mt; };
 
 // Replay instantiations: every geometry with LRU (the carbon_sim.cfg default),
 // all four policy combinations for the reference geometries.
-#define GG_KERN(A1, A2, P1, P2) { A1, A2, P1, P2, k_cache_replay<A1, A2, P1, P2>, k_quartet<A1, A2> }
+#define GG_KERN(A1, A2, P1, P2) { A1, A2, P1, P2, k_cache_replay<A1, A2, P1, P2, false>, k_quartet<A1, A2, false>, \
+                                  k_cache_replay<A1, A2, P1, P2, true>, k_quartet<A1, A2, true> }
 const Kern kKernels[] = {
   GG_KERN(4, 8, 1, 1), GG_KERN(4, 8, 0, 0), GG_KERN(4, 8, 1, 0), GG_KERN(4, 8, 0, 1),
   GG_KERN(4, 16, 1, 1), GG_KERN(4, 16, 0, 0), GG_KERN(4, 16, 1, 0), GG_KERN(4, 16, 0, 1),
@@ -1878,17 +1952,20 @@ const Kern kKernels[] = {
   GG_KERN(4, 2, 1, 1), GG_KERN(4, 32, 1, 1),
 };
 
-#define GG_LEAN(A1, A2, P1, P2) { A1, A2, P1, P2, k_cache_replay_lean<A1, A2, P1, P2>, k_quartet<A1, A2> }
-const Kern kLean[] = {
+typedef void (*lean_fn)(gg_cache_state, gg_geom, const uint64_t*, const uint32_t*, const uint64_t*,
+                        uint32_t*, uint64_t*, uint32_t*);
+struct LeanKern { int a1, a2; int lru1, lru2; lean_fn replay; };
+#define GG_LEAN(A1, A2, P1, P2) { A1, A2, P1, P2, k_cache_replay_lean<A1, A2, P1, P2> }
+const LeanKern kLean[] = {
   GG_LEAN(4, 8, 1, 1), GG_LEAN(4, 8, 0, 0), GG_LEAN(4, 8, 1, 0), GG_LEAN(4, 8, 0, 1),
   GG_LEAN(4, 4, 1, 1), GG_LEAN(2, 4, 1, 1), GG_LEAN(2, 8, 1, 1), GG_LEAN(4, 2, 1, 1),
 };
 
 using stream_fn = void (*)(gg_cache_state, gg_geom, const uint64_t*, const uint32_t*, const uint64_t*,
-                           uint32_t*, uint64_t*, uint32_t*, unsigned long long*);
+                           uint32_t*, uint64_t*, uint32_t*, unsigned long long*, MtArg<false>);
 struct StreamKern { int a1, a2, lru1, lru2, ncw; stream_fn plain, ev; };
 #define GG_STREAM(A1, A2, P1, P2, W) \
-  { A1, A2, P1, P2, W, k_cache_stream<A1, A2, P1, P2, W, false>, k_cache_stream<A1, A2, P1, P2, W, true> }
+  { A1, A2, P1, P2, W, k_cache_stream<A1, A2, P1, P2, W, false, false>, k_cache_stream<A1, A2, P1, P2, W, true, false> }
 const StreamKern kStream[] = {
   GG_STREAM(4, 8, 1, 1, 2), GG_STREAM(4, 8, 0, 0, 2), GG_STREAM(4, 8, 1, 0, 2), GG_STREAM(4, 8, 0, 1, 2),
   GG_STREAM(4, 4, 1, 1, 2), GG_STREAM(2, 4, 1, 1, 2), GG_STREAM(2, 8, 1, 1, 2), GG_STREAM(4, 2, 1, 1, 2),
@@ -1896,20 +1973,32 @@ const StreamKern kStream[] = {
   GG_STREAM(4, 16, 1, 1, 2), GG_STREAM(4, 16, 0, 0, 2),      // configs[4]: 16-way L2
 };
 
-const StreamKern* find_stream(const gg_geom& g)
+// Streaming instances with miss-type tracking: the default geometry and the
+// 16-way LRU geometry of configs[4]; every other geometry of an opted-in
+// context takes the generic tracking kernel (k_cache_replay<..., true>).
+using stream_mt_fn = void (*)(gg_cache_state, gg_geom, const uint64_t*, const uint32_t*, const uint64_t*,
+                              uint32_t*, uint64_t*, uint32_t*, unsigned long long*, MtArg<true>);
+struct StreamMtKern { int a1, a2, lru1, lru2, ncw; stream_mt_fn plain, ev; };
+#define GG_STREAM_MT(A1, A2, P1, P2, W) \
+  { A1, A2, P1, P2, W, k_cache_stream<A1, A2, P1, P2, W, false, true>, k_cache_stream<A1, A2, P1, P2, W, true, true> }
+const StreamMtKern kStreamMt[] = { GG_STREAM_MT(4, 8, 1, 1, 2), GG_STREAM_MT(4, 16, 1, 1, 2) };
+
+template <class K, size_t N>
+const K* find_stream_in(const K (&list)[N], const gg_geom& g)
 {
   const int l1 = g.pol1 == GG_POLICY_LRU, l2 = g.pol2 == GG_POLICY_LRU;
-  for (const StreamKern& k : kStream)
+  for (const K& k : list)
     if ((uint32_t)k.a1 == g.a1 && (uint32_t)k.a2 == g.a2 && k.lru1 == l1 && k.lru2 == l2 &&
         (uint32_t)k.ncw * GG_WAVE == g.u1)
       return &k;
   return nullptr;
 }
+const StreamKern* find_stream(const gg_geom& g) { return find_stream_in(kStream, g); }
 
-const Kern* find_lean(uint32_t a1, uint32_t a2, uint32_t pol1, uint32_t pol2)
+const LeanKern* find_lean(uint32_t a1, uint32_t a2, uint32_t pol1, uint32_t pol2)
 {
   const int l1 = pol1 == GG_POLICY_LRU, l2 = pol2 == GG_POLICY_LRU;
-  for (const Kern& k : kLean)
+  for (const LeanKern& k : kLean)
     if ((uint32_t)k.a1 == a1 && (uint32_t)k.a2 == a2 && k.lru1 == l1 && k.lru2 == l2) return &k;
   return nullptr;
 }
@@ -1971,8 +2060,38 @@ void gg_cache_state_free(gg_ctx* ctx)
   gg_cache_state& cs = ctx->cs;
   void* ps[] = {cs.l1_tag, cs.l1_meta, cs.l1_rr, cs.l2_tag, cs.l2_meta, cs.l2_rr, cs.counters,
                 ctx->sh_key, ctx->sh_res, ctx->sh_ev, ctx->rec_slot, ctx->chunk_cnt, ctx->chunk_tile, ctx->chunk_start,
-                ctx->chunk_len, ctx->unit_len, ctx->unit_base, ctx->tile_off_dev, ctx->total_dev};
+                ctx->chunk_len, ctx->unit_len, ctx->unit_base, ctx->tile_off_dev, ctx->total_dev,
+                ctx->mt.tab, ctx->mt.cnt};
   for (void* p : ps) if (p) hipFree(p);
+}
+
+// gg_cache_track_miss_types after its checks: the address table (every word
+// empty) and the counts
+gg_status gg_cache_mt_alloc(gg_ctx* ctx, uint64_t lines)
+{
+  const gg_geom& g = ctx->g;
+  gg_mt_view v{};
+  v.on1 = ctx->cfg.l1i_track_miss_types ? 1u : 0u;     // the L1-D takes the L1-I flag (l1_cache_cntlr.cc:69)
+  v.on2 = ctx->cfg.l2_track_miss_types ? 1u : 0u;
+  v.log_spu = (uint32_t)__builtin_ctzll(lines) - g.log_u1;
+  const size_t bytes = (size_t)g.tiles * (v.on1 + v.on2) * lines * sizeof(uint64_t);
+  const size_t cbytes = sizeof(unsigned long long) * g.tiles * 2 * GG_NUM_MISS_TYPES;
+  GG_HIP(hipMalloc((void**)&v.tab, bytes));
+  if (hipError_t e = hipMalloc((void**)&v.cnt, cbytes)) { hipFree(v.tab); return gg_hip_check(e, "hipMalloc(miss types)"); }
+  hipStream_t s = ctx->last_stream;
+  GG_HIP(hipMemsetAsync(v.tab, 0xFF, bytes, s));
+  GG_HIP(hipMemsetAsync(v.cnt, 0, cbytes, s));
+  GG_HIP(hipStreamSynchronize(s));
+  if (ctx->mt.tab) { hipFree(ctx->mt.tab); hipFree(ctx->mt.cnt); }   // a fresh context sized again
+  ctx->mt = v;
+  ctx->mt_lines = lines;
+  return GG_OK;
+}
+
+gg_status gg_cache_mt_counts(gg_ctx* ctx, uint64_t* out)
+{
+  GG_HIP(hipMemcpy(out, ctx->mt.cnt, sizeof(uint64_t) * ctx->g.tiles * 2 * GG_NUM_MISS_TYPES, hipMemcpyDeviceToHost));
+  return GG_OK;
 }
 
 gg_status gg_cache_state_reset(gg_ctx* ctx, hipStream_t s)
@@ -1982,6 +2101,11 @@ gg_status gg_cache_state_reset(gg_ctx* ctx, hipStream_t s)
   hipLaunchKernelGGL(k_state_reset, dim3(blocks), dim3(256), 0, s, ctx->cs, g);
   GG_HIP(hipGetLastError());
   GG_HIP(hipMemsetAsync(ctx->cs.counters, 0, sizeof(uint64_t) * g.tiles * 2 * GG_NUM_CACHE_COUNTERS, s));
+  if (ctx->mt.tab) {                                   // an opted-in context stays opted in: empty table, zero counts
+    GG_HIP(hipMemsetAsync(ctx->mt.tab, 0xFF, (size_t)g.tiles * (ctx->mt.on1 + ctx->mt.on2) * ctx->mt_lines * sizeof(uint64_t), s));
+    GG_HIP(hipMemsetAsync(ctx->mt.cnt, 0, sizeof(unsigned long long) * g.tiles * 2 * GG_NUM_MISS_TYPES, s));
+  }
+  ctx->cache_dirty = false;
   return GG_OK;
 }
 
@@ -1992,6 +2116,7 @@ gg_status gg_cache_run_batch(gg_ctx* ctx, const gg_trace* tr, uint32_t* result, 
   if (tr->tile_offsets[0] != 0 || tr->tile_offsets[g.tiles] != tr->num_records)
     return gg_fail(GG_ERR_INVALID, "tile_offsets must run from 0 to num_records");
   if (tr->num_records && (!tr->addr_dev || !tr->meta_dev)) return gg_fail(GG_ERR_INVALID, "addr/meta device pointers are NULL");
+  ctx->cache_dirty = true;
   // ---- default: the single-pass streaming replay ----
   if (ctx->replay_variant == 0) {
     const StreamKern* sk = find_stream(g);
@@ -2002,10 +2127,17 @@ gg_status gg_cache_run_batch(gg_ctx* ctx, const gg_trace* tr, uint32_t* result, 
       max_len = std::max<uint64_t>(max_len, tr->tile_offsets[t + 1] - tr->tile_offsets[t]);
     }
     const uint32_t log_s2 = (uint32_t)__builtin_ctz(g.s2);
-    if (sk && lds <= 160 * 1024 && g.s2 * g.a2 < 255 && max_len < (1ull << (31 - log_s2))) {
+    // an opted-in context (miss-type tracking) streams where a tracking
+    // instance exists, else it falls through to the generic tracking kernel
+    const bool track = ctx->mt.tab != nullptr;
+    const StreamMtKern* skm = track ? find_stream_in(kStreamMt, g) : nullptr;
+    if (track) sk = nullptr;
+    if ((sk || skm) && lds <= 160 * 1024 && g.s2 * g.a2 < 255 && max_len < (1ull << (31 - log_s2))) {
       GG_HIP(hipMemcpyAsync(ctx->tile_off_dev, tr->tile_offsets, sizeof(uint64_t) * (g.tiles + 1), hipMemcpyHostToDevice, s));
-      stream_fn fn = evicted ? sk->ev : sk->plain;
-      GG_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      const stream_fn fn = sk ? (evicted ? sk->ev : sk->plain) : nullptr;
+      const stream_mt_fn fn_mt = skm ? (evicted ? skm->ev : skm->plain) : nullptr;
+      const uint32_t ncw = (uint32_t)(sk ? sk->ncw : skm->ncw);
+      GG_HIP(hipFuncSetAttribute(sk ? (const void*)fn : (const void*)fn_mt, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       gg_timer_begin(ctx, "cache_stream", s);
       // GG_STREAM_DEBUG=1: hand-off counters of the launch on stderr (diagnostics);
       // GG_STREAM_BAD_INDEX=1 (test knob, read per batch): a broken hand-off
@@ -2020,9 +2152,14 @@ gg_status gg_cache_run_batch(gg_ctx* ctx, const gg_trace* tr, uint32_t* result, 
         if (dbg_on == 2) GG_HIP(hipMemsetAsync(dbg + 7, 1, 1, s));   // GG_STREAM_DEBUG=2: skip the cache step (builds with -DGG_STREAM_NOSTEP)
         if (bad_index) GG_HIP(hipMemsetAsync(dbg + 6, 1, 1, s));
       }
-      hipLaunchKernelGGL(fn, dim3(g.tiles), dim3((sk->ncw + 1) * GG_WAVE), lds, s, ctx->cs, g, tr->addr_dev,
-                         tr->meta_dev, (const uint64_t*)ctx->tile_off_dev, result, evicted,
-                         ctx->err_dev, dbg);
+      if (sk)
+        hipLaunchKernelGGL(fn, dim3(g.tiles), dim3((ncw + 1) * GG_WAVE), lds, s, ctx->cs, g, tr->addr_dev,
+                           tr->meta_dev, (const uint64_t*)ctx->tile_off_dev, result, evicted,
+                           ctx->err_dev, dbg, MtArg<false>{});
+      else
+        hipLaunchKernelGGL(fn_mt, dim3(g.tiles), dim3((ncw + 1) * GG_WAVE), lds, s, ctx->cs, g, tr->addr_dev,
+                           tr->meta_dev, (const uint64_t*)ctx->tile_off_dev, result, evicted,
+                           ctx->err_dev, dbg, MtArg<true>{ctx->mt, ctx->err_dev});
       GG_HIP(hipGetLastError());
       gg_timer_end(ctx, "cache_stream", s);
       if (dbg) {
@@ -2111,13 +2248,24 @@ gg_status gg_cache_run_batch(gg_ctx* ctx, const gg_trace* tr, uint32_t* result, 
     GG_HIP(hipGetLastError());
     gg_timer_end(ctx, "cache_scatter", s);
   }
-  const Kern* lean = find_lean(g.a1, g.a2, g.pol1, g.pol2);
-  const Kern* k = (ctx->replay_variant != 1 && lean) ? lean : find_kernel(g.a1, g.a2, g.pol1, g.pol2);
+  // (an opted-in context: the generic kernel's tracking instance, whatever replay_kernel says)
+  const LeanKern* lean = (ctx->mt.tab || ctx->replay_variant == 1) ? nullptr : find_lean(g.a1, g.a2, g.pol1, g.pol2);
+  const Kern* k = find_kernel(g.a1, g.a2, g.pol1, g.pol2);
   const uint32_t groups = (uint32_t)((g.units + GG_WAVE - 1) / GG_WAVE);
   gg_timer_begin(ctx, "cache_replay", s);
-  hipLaunchKernelGGL(k->replay, dim3(groups), dim3(GG_WAVE), replay_lds_bytes(g, k == lean), s, ctx->cs, g,
-                     (const uint64_t*)ctx->sh_key, (const uint32_t*)ctx->unit_len, (const uint64_t*)ctx->unit_base,
-                     result ? ctx->sh_res : nullptr, evicted ? ctx->sh_ev : nullptr, ctx->err_dev);
+  if (ctx->mt.tab)
+    hipLaunchKernelGGL(k->replay_mt, dim3(groups), dim3(GG_WAVE), replay_lds_bytes(g, false), s, ctx->cs, g,
+                       (const uint64_t*)ctx->sh_key, (const uint32_t*)ctx->unit_len, (const uint64_t*)ctx->unit_base,
+                       result ? ctx->sh_res : nullptr, evicted ? ctx->sh_ev : nullptr, ctx->err_dev,
+                       MtArg<true>{ctx->mt, ctx->err_dev});
+  else if (lean)
+    hipLaunchKernelGGL(lean->replay, dim3(groups), dim3(GG_WAVE), replay_lds_bytes(g, true), s, ctx->cs, g,
+                       (const uint64_t*)ctx->sh_key, (const uint32_t*)ctx->unit_len, (const uint64_t*)ctx->unit_base,
+                       result ? ctx->sh_res : nullptr, evicted ? ctx->sh_ev : nullptr, ctx->err_dev);
+  else
+    hipLaunchKernelGGL(k->replay, dim3(groups), dim3(GG_WAVE), replay_lds_bytes(g, false), s, ctx->cs, g,
+                       (const uint64_t*)ctx->sh_key, (const uint32_t*)ctx->unit_len, (const uint64_t*)ctx->unit_base,
+                       result ? ctx->sh_res : nullptr, evicted ? ctx->sh_ev : nullptr, ctx->err_dev, MtArg<false>{});
   GG_HIP(hipGetLastError());
   gg_timer_end(ctx, "cache_replay", s);
   if (n && (result || evicted)) {
@@ -2146,7 +2294,12 @@ gg_status gg_cache_quartet(gg_ctx* ctx, int op, uint32_t tile, int level, uint64
   GG_HIP(hipMalloc((void**)&d, sizeof(QuartetIO)));
   hipStream_t s = ctx->last_stream;
   GG_HIP(hipMemcpyAsync(d, &q, sizeof(q), hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(find_kernel(g.a1, g.a2, g.pol1, g.pol2)->quartet, dim3(1), dim3(1), 0, s, ctx->cs, g, d);
+  ctx->cache_dirty = true;
+  const Kern* k = find_kernel(g.a1, g.a2, g.pol1, g.pol2);
+  if (ctx->mt.tab)
+    hipLaunchKernelGGL(k->quartet_mt, dim3(1), dim3(1), 0, s, ctx->cs, g, d, MtArg<true>{ctx->mt, ctx->err_dev});
+  else
+    hipLaunchKernelGGL(k->quartet, dim3(1), dim3(1), 0, s, ctx->cs, g, d, MtArg<false>{});
   GG_HIP(hipGetLastError());
   GG_HIP(hipMemcpyAsync(&q, d, sizeof(q), hipMemcpyDeviceToHost, s));
   GG_HIP(hipStreamSynchronize(s));

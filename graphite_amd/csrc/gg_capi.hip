@@ -254,6 +254,11 @@ static gg_status check_device_errors(gg_ctx* ctx)
   if (e & GG_DERR_RANGE) return gg_fail(GG_ERR_RANGE, "a trace address is beyond the compressed-tag range (%#llx)",
                                         (unsigned long long)ctx->g.addr_limit);
   if (e & GG_DERR_STATE) return gg_fail(GG_ERR_STATE, "cache state the reference would reject (LOG_ASSERT_ERROR)");
+  if (e & GG_DERR_MT_CAP)
+    return gg_fail(GG_ERR_UNSUPPORTED, "miss-type tracking: some (tile, L1-D set) holds more than %llu distinct lines "
+                   "(capacity %llu lines per (tile, cache), set by gg_cache_track_miss_types); the miss-type counts "
+                   "are void until gg_reset", (unsigned long long)(ctx->mt_lines / ctx->g.u1),
+                   (unsigned long long)ctx->mt_lines);
   if (e & GG_DERR_CAP) return gg_fail(GG_ERR_HIP, "a device-side capacity or hand-off bound was exceeded");
   return GG_OK;
 }
@@ -262,12 +267,44 @@ gg_status gg_cache_access_batch(gg_ctx* ctx, const gg_trace* trace, uint32_t* re
                                 uint64_t* evicted_dev, void* stream)
 {
   if (!ctx) return gg_fail(GG_ERR_INVALID, "ctx NULL");
-  if (ctx->cfg.l1i_track_miss_types || ctx->cfg.l2_track_miss_types)
-    return gg_fail(GG_ERR_UNSUPPORTED, "miss-type tracking is built for the coherent mode only");
+  if ((ctx->cfg.l1i_track_miss_types || ctx->cfg.l2_track_miss_types) && !ctx->mt.tab)
+    return gg_fail(GG_ERR_UNSUPPORTED, "miss-type tracking is built for the coherent mode only "
+                   "(the private replay tracks after gg_cache_track_miss_types)");
   hipSetDevice(ctx->device);
   hipStream_t s = (hipStream_t)stream;
   ctx->last_stream = s;
   return gg_cache_run_batch(ctx, trace, result_dev, evicted_dev, s);
+}
+
+gg_status gg_cache_track_miss_types(gg_ctx* ctx, uint32_t lines)
+{
+  if (!ctx) return gg_fail(GG_ERR_INVALID, "ctx NULL");
+  const gg_config& c = ctx->cfg;
+  if (!c.l1i_track_miss_types && !c.l2_track_miss_types)
+    return gg_fail(GG_ERR_INVALID, "gg_cache_track_miss_types: neither l1i_track_miss_types (the L1-D's flag) nor "
+                   "l2_track_miss_types is set");
+  const uint64_t n = lines ? lines : (c.miss_track_lines ? c.miss_track_lines : 65536u);
+  if (!is_pow2(n) || n < 8ull * ctx->g.u1 || n > (1ull << 26))
+    return gg_fail(GG_ERR_INVALID, "gg_cache_track_miss_types: %llu lines (a power of two from 8 x %u L1-D sets to 2^26)",
+                   (unsigned long long)n, ctx->g.u1);
+  if (ctx->g.log_line < 3)
+    return gg_fail(GG_ERR_UNSUPPORTED, "gg_cache_track_miss_types: lines of less than 8 bytes");
+  if (ctx->cache_dirty)
+    return gg_fail(GG_ERR_STATE, "gg_cache_track_miss_types: the private cache state is not fresh (call it after "
+                   "gg_create or gg_reset, before any batch or quartet call): the sets would miss the resident lines");
+  hipSetDevice(ctx->device);
+  return gg_cache_mt_alloc(ctx, n);
+}
+
+gg_status gg_cache_get_miss_types(gg_ctx* ctx, uint64_t* out)
+{
+  if (!ctx || !out) return gg_fail(GG_ERR_INVALID, "NULL argument");
+  if (!ctx->mt.tab) return gg_fail(GG_ERR_INVALID, "gg_cache_get_miss_types: the context is not opted in "
+                                   "(gg_cache_track_miss_types)");
+  hipSetDevice(ctx->device);
+  GG_HIP(hipStreamSynchronize(ctx->last_stream));
+  if (gg_status st = gg_cache_mt_counts(ctx, out)) return st;
+  return check_device_errors(ctx);
 }
 
 gg_status gg_cache_get_counters(gg_ctx* ctx, uint64_t* out)

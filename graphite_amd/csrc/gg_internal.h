@@ -31,6 +31,7 @@
 #define GG_DERR_BARRIER 8u // a BARRIER record (GG_META_BARRIER) reached a path that has no barriers (Mode P)
 #define GG_DERR_SAMPLES 16u // the statistics trace's sample buffer is full (gg_stats.hip)
 #define GG_DERR_SHARERS 32u // the statistics trace's scan met a directory entry with more sharers than tiles
+#define GG_DERR_MT_CAP 64u  // Mode P miss-type tracking: a (tile, L1-D set) slice of the address table is full (gg_modep_mt.h)
 
 // Geometry derived from gg_config (cache.cc:44, cache_hash_fn.h:11).
 struct gg_geom {
@@ -59,6 +60,16 @@ struct gg_cache_state {
   uint64_t* l2_meta;  // [s2*mw][units]   byte (w%8) of word w/8
   uint8_t*  l2_rr;    // [s2][units]
   uint64_t* counters; // [tiles][2][GG_NUM_CACHE_COUNTERS]
+};
+
+// Mode P miss-type tracking (gg_cache_track_miss_types; the device side is
+// gg_modep_mt.h): the address table [tile][tracked cache][L1-D set][slot] and
+// the counts, as the kernels see them.  tab == nullptr: not opted in.
+struct gg_mt_view {
+  uint64_t* tab;
+  unsigned long long* cnt;   // [tiles][2][GG_NUM_MISS_TYPES]
+  uint32_t log_spu;          // log2(slots per (tile, cache, L1-D set))
+  uint32_t on1, on2;         // L1-D / L2 tracked
 };
 
 struct gg_timer {
@@ -105,6 +116,12 @@ struct gg_ctx {
   gg_coh_state* coh = nullptr;
   // replay kernel choice: 0 = lean when instantiated (default), 1 = generic
   int replay_variant = 0;
+  // Mode P miss-type tracking (gg_cache_track_miss_types): the table, its
+  // capacity per (tile, cache) in lines, and whether the private cache state
+  // has been touched since gg_create / gg_reset (the opt-in needs it fresh)
+  gg_mt_view mt{};
+  uint64_t mt_lines = 0;
+  bool cache_dirty = false;
   // timing
   int timing = 0;                // gg_set_timing: 0 off, 1 sampled coherent launches, 2 every launch
   std::vector<gg_timer> timers;
@@ -150,6 +167,8 @@ gg_status gg_cache_state_reset(gg_ctx* ctx, hipStream_t s);
 gg_status gg_cache_run_batch(gg_ctx* ctx, const gg_trace* tr, uint32_t* result, uint64_t* evicted, hipStream_t s);
 gg_status gg_cache_quartet(gg_ctx* ctx, int op, uint32_t tile, int level, uint64_t addr,
                            const gg_line_info* in, gg_line_info* out, int* eviction, uint64_t* ev_addr);
+gg_status gg_cache_mt_alloc(gg_ctx* ctx, uint64_t lines);      // gg_cache_track_miss_types, after its checks
+gg_status gg_cache_mt_counts(gg_ctx* ctx, uint64_t* out);      // [tiles][2][GG_NUM_MISS_TYPES]
 
 // NoC path (gg_noc.hip)
 gg_status gg_noc_alloc(gg_ctx* ctx);

@@ -39,6 +39,10 @@ gg_status gg_dump_summary(gg_ctx* ctx, int format, char* buf, uint64_t cap, uint
     mt.resize((size_t)T * 2 * GG_NUM_MISS_TYPES);
     if (gg_status e = gg_coherent_get_miss_types(ctx, mt.data())) return e;
   }
+  if (!coherent && ctx->mt.tab) {              // a private context opted in with gg_cache_track_miss_types
+    mt.resize((size_t)T * 2 * GG_NUM_MISS_TYPES);
+    if (gg_status e = gg_cache_get_miss_types(ctx, mt.data())) return e;
+  }
   std::vector<uint64_t> core;
   if (ctx->core_valid) {                       // gg_core_model_run's statistics: the "Core Summary" blocks
     core.resize((size_t)T * GG_NUM_CORE_STATS);

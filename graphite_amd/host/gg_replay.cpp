@@ -6,6 +6,10 @@
 //       synthetic configs[1] trace, generated on the host
 //   gg_replay --tiles T --trace FILE [--batches B]
 //       FILE: little-endian records {u32 tile, u32 meta, u64 byte address}
+//   gg_replay --tiles T ... --miss-types LINES
+//       the private replay with both caches' miss types tracked
+//       (gg_cache_track_miss_types, LINES per (tile, cache), 0 = the default):
+//       a "Miss Types" block under each cache
 //   gg_replay --coherent --tiles T --per-tile N [--hot-lines H] [--net hop_counter|hop_by_hop|magic]
 //       coherent mode (MSI directory + DRAM + NoC, gg_coherent_run) on the
 //       configs[2..4] hotspot trace generated on the device; prints every
@@ -66,7 +70,8 @@ static uint64_t splitmix_at(uint64_t seed, uint64_t i)
 int main(int argc, char** argv)
 {
   uint32_t tiles = 4, lines_log2 = 15, batches = 1, l2_assoc = 8, hot_lines = 64, net = GG_NET_EMESH_HOP_COUNTER;
-  bool coherent = false, table = false;
+  bool coherent = false, table = false, miss_types = false;
+  uint32_t miss_lines = 0;
   uint64_t per_tile = 100000;
   std::string trace, id_file, stats_dir;
   uint64_t sampling_interval = 10000, max_samples = 4096;
@@ -82,6 +87,7 @@ int main(int argc, char** argv)
     else if (a == "--batches") batches = (uint32_t)std::strtoul(next(), nullptr, 0);
     else if (a == "--l2-assoc") l2_assoc = (uint32_t)std::strtoul(next(), nullptr, 0);
     else if (a == "--trace") trace = next();
+    else if (a == "--miss-types") { miss_types = true; miss_lines = (uint32_t)std::strtoul(next(), nullptr, 0); }
     else if (a == "--coherent") coherent = true;
     else if (a == "--stats-trace") stats_dir = next();
     else if (a == "--sampling-interval") sampling_interval = std::strtoull(next(), nullptr, 0);
@@ -325,7 +331,9 @@ int main(int argc, char** argv)
     gg_config cfg;
     gg_config_default(&cfg, tiles);
     cfg.l2_assoc = l2_assoc;
+    if (miss_types) cfg.l1i_track_miss_types = cfg.l2_track_miss_types = 1;   // (the L1-D takes the L1-I flag)
     Backend be(cfg);
+    if (miss_types) check(gg_cache_track_miss_types(be.ctx(), miss_lines), "gg_cache_track_miss_types");
     TraceReplayer rep(be);
     std::vector<std::vector<std::pair<uint64_t, uint32_t>>> recs(tiles);
     if (!trace.empty()) {
@@ -355,7 +363,7 @@ int main(int argc, char** argv)
       }
       for (uint32_t r : rep.flush()) misses += (r & GG_RES_L1_MISS) != 0;
     }
-    rep.outputSummary(std::cout);
+    rep.outputSummary(std::cout, miss_types);
     std::cout << "L1-D misses reported per access: " << misses << std::endl;
   } catch (const Error& e) {
     std::fprintf(stderr, "gg_replay: %s\n", e.what());

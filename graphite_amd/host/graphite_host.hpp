@@ -505,9 +505,12 @@ inline void writeTileSummary(std::ostream& os, const gg_config& cfg, const uint6
   else if (core_stats) writeCoreSummary(os, core_stats, cfg.frequency_ghz);
   if (tile_stats) writeMemorySummary(os, cfg, tile_stats, cache_counters, miss_types, proto);
   else {
+    // (miss_types: a context opted in with gg_cache_track_miss_types; the L1-D takes the L1-I flag)
     os << "Cache Summary:\n";
-    writeCacheSummary(os, "L1-D", cache_counters, false);
-    writeCacheSummary(os, "L2", cache_counters + GG_NUM_CACHE_COUNTERS, true);
+    writeCacheSummary(os, "L1-D", cache_counters, false, false,
+                      miss_types && cfg.l1i_track_miss_types ? miss_types : nullptr);
+    writeCacheSummary(os, "L2", cache_counters + GG_NUM_CACHE_COUNTERS, true, false,
+                      miss_types && cfg.l2_track_miss_types ? miss_types + GG_NUM_MISS_TYPES : nullptr);
   }
   os << "Network Summary: " << std::endl << "  Network (User): " << std::endl;
   writeNetworkSummary(os, zero_net, cfg.frequency_ghz, GG_NET_EMESH_HOP_COUNTER);
@@ -746,13 +749,24 @@ class TraceReplayer {
 
   // "Cache Summary:" block of every tile (MemoryManager::outputSummary,
   // pr_l1_pr_l2_dram_directory_msi/memory_manager.cc:415-430, L1-D and L2 only)
-  void outputSummary(std::ostream& out) const
+  // miss_types: the context is opted in (gg_cache_track_miss_types): the
+  // "Miss Types" block under each tracked cache
+  void outputSummary(std::ostream& out, bool miss_types = false) const
   {
     std::vector<uint64_t> c = _be.cacheCounters();
-    for (uint32_t t = 0; t < _be.config().num_tiles; ++t) {
+    const gg_config& cfg = _be.config();
+    std::vector<uint64_t> mt;
+    if (miss_types) {
+      mt.resize((size_t)cfg.num_tiles * 2 * GG_NUM_MISS_TYPES);
+      check(gg_cache_get_miss_types(_be.ctx(), mt.data()), "gg_cache_get_miss_types");
+    }
+    for (uint32_t t = 0; t < cfg.num_tiles; ++t) {
+      const uint64_t* m = miss_types ? &mt[(size_t)t * 2 * GG_NUM_MISS_TYPES] : nullptr;
       out << "Tile " << t << " Cache Summary:" << std::endl;
-      writeCacheSummary(out, "L1-D", &c[((size_t)t * 2 + 0) * GG_NUM_CACHE_COUNTERS], false);
-      writeCacheSummary(out, "L2", &c[((size_t)t * 2 + 1) * GG_NUM_CACHE_COUNTERS], true);
+      writeCacheSummary(out, "L1-D", &c[((size_t)t * 2 + 0) * GG_NUM_CACHE_COUNTERS], false, false,
+                        m && cfg.l1i_track_miss_types ? m : nullptr);
+      writeCacheSummary(out, "L2", &c[((size_t)t * 2 + 1) * GG_NUM_CACHE_COUNTERS], true, false,
+                        m && cfg.l2_track_miss_types ? m + GG_NUM_MISS_TYPES : nullptr);
     }
   }
 

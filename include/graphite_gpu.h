@@ -227,7 +227,9 @@ typedef struct gg_config {
                                     footprint; allocated when tracking is on:
                                     tiles x 2 x lines x 8 B (65536: 1 GiB at 1024 tiles,
                                     4 GiB at 4096).  A full table stops the run with
-                                    GG_ERR_UNSUPPORTED (no set entry is overwritten). */
+                                    GG_ERR_UNSUPPORTED (no set entry is overwritten).
+                                    Also the default capacity of the private replay's
+                                    table (gg_cache_track_miss_types with lines = 0). */
   /* ---- caching protocol (caching_protocol/type, carbon_sim.cfg:184) ---- */
   uint32_t protocol;             /* GG_PROTO_*: pr_l1_pr_l2_dram_directory_msi (0) / _mosi (1) /
                                     pr_l1_sh_l2_msi (2) / pr_l1_sh_l2_mesi (3)                */
@@ -440,6 +442,37 @@ gg_status gg_cache_access_batch(gg_ctx* ctx, const gg_trace* trace,
  * [tile][level][counter].  Synchronizes the context's stream.                */
 gg_status gg_cache_get_counters(gg_ctx* ctx, uint64_t* out);
 
+/* Opt a context into miss-type tracking (Cache track_miss_types, cache.cc:321-405)
+ * for the private replay and the Cache quartet.  Tracked caches, as in the
+ * reference: the L1-D takes cfg.l1i_track_miss_types (l1_cache_cntlr.cc:69),
+ * the L2 cfg.l2_track_miss_types; GG_ERR_INVALID with neither set.  A context
+ * with a flag set that has not made this call keeps refusing
+ * gg_cache_access_batch (GG_ERR_UNSUPPORTED).
+ * lines: capacity of the address sets per (tile, cache) in lines; 0 means
+ * cfg.miss_track_lines, and 65536 if that is 0 too; a power of two, at least
+ * 8 x the L1-D sets and at most 2^26, else GG_ERR_INVALID.  Allocates
+ * tiles x (tracked caches) x lines x 8 B; gg_reset empties the table and
+ * zeroes the counts (the context stays opted in), gg_destroy frees it.
+ * Only on a fresh private cache state: after gg_create or gg_reset, before any
+ * batch or quartet call; GG_ERR_STATE otherwise (the sets would miss the
+ * lines already resident).
+ * Capacity rule: the table is partitioned by (tile, L1-D set), lines / L1-D
+ * sets slots each, and keeps every distinct line a set ever installed.  A
+ * run fails exactly when some (tile, L1-D set) has to hold more distinct lines
+ * than lines / L1-D sets (both caches of a tile see the same lines, so one rule
+ * covers both): gg_cache_get_counters and gg_cache_get_miss_types then return
+ * GG_ERR_UNSUPPORTED, no slot is overwritten, and the miss-type counts are
+ * void until gg_reset.  On an opted-in context every replay_kernel value
+ * runs a tracking kernel: 0 streams for the default and the 16-way-L2 LRU
+ * geometries and takes the sharded generic kernel elsewhere, 1 and 2 take the
+ * sharded generic kernel.                                                    */
+gg_status gg_cache_track_miss_types(gg_ctx* ctx, uint32_t lines);
+/* The miss types of the private replay and the quartet: out
+ * [tiles][2][GG_NUM_MISS_TYPES] (L1-D, L2), zeros for an untracked cache.
+ * GG_ERR_INVALID on a context that is not opted in.  Synchronizes the
+ * context's stream and reports device errors like gg_cache_get_counters.     */
+gg_status gg_cache_get_miss_types(gg_ctx* ctx, uint64_t* out);
+
 /* The Cache quartet on one tile's device-resident cache (slow path, one line
  * per call; used by the host mirror classes and the parity tests).           */
 gg_status gg_cache_get_line_info(gg_ctx* ctx, uint32_t tile, int level,
@@ -633,8 +666,10 @@ gg_status gg_coherent_get_stats(gg_ctx* ctx, uint64_t* tile_stats, uint64_t* cac
  * cache.  Cache::getMissType (cache.cc:363-375) over the evicted /
  * invalidated / fetched address sets that insertCacheLine and
  * setCacheLineInfo keep (cache.cc:131-148, 228-230, 398-404).  The private
- * (Mode P) replay does not track them: gg_cache_access_batch returns
- * GG_ERR_UNSUPPORTED when either flag is set.                                */
+ * (Mode P) replay tracks them on a context opted in with
+ * gg_cache_track_miss_types (counts: gg_cache_get_miss_types); without that
+ * call gg_cache_access_batch returns GG_ERR_UNSUPPORTED when either flag is
+ * set.                                                                       */
 gg_status gg_coherent_get_miss_types(gg_ctx* ctx, uint64_t* out);
 /* The MOSI event counters of a coherent run: out [tiles][GG_NUM_PROTO_STATS]
  * (zeros under MSI; tiles a context does not own read 0).                   */
