@@ -64,7 +64,8 @@ EXPORTS = ["gg_abi_version", "gg_last_error", "gg_config_default", "gg_create", 
            "gg_round_pack", "gg_round_unpack", "gg_round_finish", "gg_coherent_run_many",
            "gg_stats_trace_configure", "gg_stats_trace_sample", "gg_stats_trace_get", "gg_stats_trace_dump",
            "gg_atac_params_default", "gg_noc_set_atac", "gg_atac_topology", "gg_noc_get_atac_counters",
-           "gg_cache_track_miss_types", "gg_cache_get_miss_types"]
+           "gg_cache_track_miss_types", "gg_cache_get_miss_types",
+           "gg_coherent_advance", "gg_coherent_snapshot_size", "gg_coherent_snapshot", "gg_coherent_restore"]
 
 # statistics trace (gg_stats_trace_*): GG_ST_* statistics bits, GG_STF_* sample fields
 ST_NETWORK_UTILIZATION, ST_CACHE_LINE_REPLICATION = 1, 2
@@ -169,6 +170,12 @@ def load():
     L.gg_cache_track_miss_types.argtypes = [vp, u32]
     L.gg_cache_get_miss_types.argtypes = [vp, vp]
     for name in ["gg_cache_track_miss_types", "gg_cache_get_miss_types"]:
+        getattr(L, name).restype = i32
+    L.gg_coherent_advance.argtypes = [vp, u64, ctypes.POINTER(u64), ctypes.POINTER(i32)]
+    L.gg_coherent_snapshot_size.argtypes = [vp, ctypes.POINTER(u64)]
+    L.gg_coherent_snapshot.argtypes = [vp, vp, u64, ctypes.POINTER(u64)]
+    L.gg_coherent_restore.argtypes = [vp, ctypes.POINTER(_Trace), vp, vp, u64, vp]
+    for name in ["gg_coherent_advance", "gg_coherent_snapshot_size", "gg_coherent_snapshot", "gg_coherent_restore"]:
         getattr(L, name).restype = i32
     for name in ["gg_kernel_stats", "gg_shard_map", "gg_coherent_begin", "gg_coherent_quantum", "gg_coherent_export",
                  "gg_coherent_import", "gg_coherent_run", "gg_coherent_get_stats", "gg_gen_hotspot_trace",
@@ -392,6 +399,50 @@ class Backend:
             _need_dev(out, torch.int64, addr.numel())
         tr = self._trace(addr, meta, tile_offsets)
         _check(load().gg_coherent_begin(self.h, ctypes.byref(tr), _ptr(out), _stream(stream)))
+
+    # ---- a run in legs: pause, snapshot, restore (gg_coherent_advance / _snapshot / _restore)
+    NEVER = 0xFFFFFFFFFFFFFFFF          # stop_quantum that never pauses
+
+    def coherent_advance(self, stop_quantum=NEVER):
+        """The device-driven loop from the current state (after coherent_begin
+        or coherent_restore) until the run is over or the next quantum is >=
+        stop_quantum.  Returns (next_quantum, done): done 0 paused, 1 over
+        (a deadlock raises, as coherent_run does)."""
+        nq, done = ctypes.c_uint64(0), ctypes.c_int(0)
+        _check(load().gg_coherent_advance(self.h, stop_quantum, ctypes.byref(nq), ctypes.byref(done)))
+        return nq.value, done.value
+
+    def coherent_snapshot_size(self):
+        n = ctypes.c_uint64(0)
+        _check(load().gg_coherent_snapshot_size(self.h, ctypes.byref(n)))
+        return n.value
+
+    def coherent_snapshot(self, cap=None):
+        """The run's state at the device loop's clean point as a numpy uint8
+        array (the container of gg_snapshot.h).  cap: the buffer's size
+        (default: what gg_coherent_snapshot_size asks for)."""
+        n = ctypes.c_uint64(self.coherent_snapshot_size() if cap is None else cap)
+        buf = np.empty(max(n.value, 1), np.uint8)
+        got = ctypes.c_uint64(0)
+        rc = load().gg_coherent_snapshot(self.h, buf.ctypes.data_as(ctypes.c_void_p), n.value, ctypes.byref(got))
+        if rc != GG_OK:
+            e = GGError(rc, load().gg_last_error().decode(errors="replace"))
+            e.needed = got.value         # GG_ERR_RANGE: the bytes a snapshot needs
+            raise e
+        return buf[:got.value]
+
+    def coherent_restore(self, blob, addr, meta, tile_offsets, out=None, stream=None):
+        """Reset as coherent_begin does, then put a snapshot's state back; the
+        run continues with coherent_advance.  out: the access-word buffer
+        (words of records already passed are not rewritten: carry the buffer
+        across for the whole array)."""
+        import torch
+        if out is not None:
+            _need_dev(out, torch.int64, addr.numel())
+        b = np.ascontiguousarray(np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray)) else blob, np.uint8)
+        tr = self._trace(addr, meta, tile_offsets)
+        _check(load().gg_coherent_restore(self.h, ctypes.byref(tr), _ptr(out), b.ctypes.data_as(ctypes.c_void_p),
+                                          b.size, _stream(stream)))
 
     def round_pack(self, world, rank, q):
         """gg_round_pack: quantum q's steps + the tail on the context's stream;

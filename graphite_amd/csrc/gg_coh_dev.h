@@ -136,9 +136,14 @@ struct Seg { uint32_t line, lo, hi, pad; };       // a run of row (X) / column (
 // of its step 0, run over, quantum-end arrivals, active / blocked tiles, least
 // next start, quanta completed, quantum length
 enum { QS_Q = 0, QS_START, QS_DONE, QS_ARRIVED, QS_ACTIVE, QS_BLOCKED, QS_MIN_NEXT, QS_COUNT, QS_QPS,
-       QS_BWAIT, QS_BMAX, QS_REL, QS_N };   // barrier waits, their latest arrival, release (max + 1, or 0)
+       QS_BWAIT, QS_BMAX, QS_REL, QS_STOP, QS_N };   // barrier waits, their latest arrival, release (max + 1, or 0), pause quantum
 // QS_REL is also written by the multi-rank round (k_c_round_commit, from the
 // ranks' gathered status words) for step 0 of its next host-indexed quantum
+// QS_DONE: 0 running, 1 over, 2 deadlock, kQsPaused: gg_coherent_advance's
+// stop (QS_STOP) reached at a quantum boundary — the launches left in the
+// batch return as after a finished run, and the rest of the quantum state
+// says where the run continues (the host clears the word to resume)
+constexpr uint64_t kQsPaused = 4;
 constexpr uint32_t kBarWait = 2;          // Tile::blocked of a tile waiting at a BARRIER record
 // gap cycles before a record (a BARRIER record is taken at the tile's clock)
 __device__ __forceinline__ uint64_t rec_gap(uint32_t meta)
@@ -2756,6 +2761,9 @@ __device__ __forceinline__ void qend_pick(const CS& S, uint32_t L, uint64_t q, u
   qs[QS_ARRIVED] = 0; qs[QS_ACTIVE] = 0; qs[QS_BLOCKED] = 0; qs[QS_MIN_NEXT] = ~0ull;
   qs[QS_BWAIT] = 0; qs[QS_BMAX] = 0; qs[QS_REL] = rel;
   qs[QS_Q] = nq; qs[QS_START] = L + 1; qs[QS_COUNT] = Q + 1;
+  // the pause of gg_coherent_advance: once per quantum, here, where the state
+  // is whole (held records imported, ring zeroed, release stored)
+  if (!done && nq >= qs[QS_STOP]) done = kQsPaused;
   qs[QS_DONE] = done;
   __threadfence();
 }
@@ -4281,5 +4289,21 @@ hipError_t persist_lc_occ(size_t lds, int* per_cu);
 void launch_walk(bool pipe, bool rq, uint32_t blocks, uint32_t threads, size_t lds, hipStream_t s, const StepArgs& a,
                  uint32_t L, int stage, bool qend);
 hipError_t walk_set_lds(size_t lds);
+
+// ---- the packed sections of a snapshot (gg_snapshot.hip) ----
+// One per-tile array of `n` slots a tile (L tiles) and what rides with a
+// slot; a record is rw = 1 + (PK_TAB ? 1 : 2 + W + (rng ? 1 : 0)) words:
+// {tile * n + slot, the slot's words}.
+enum { PK_DIR = 0, PK_REP, PK_TAB };     // 16-B entries in use; the replaced list's live entries; 8-B words != ~0
+struct PackSrc {
+  void* ent; uint64_t* sh; uint64_t* rng; const TileSt* ts;    // entries, [slot][W] sharer words, Random words (MOSI), PK_REP: nrep
+  uint32_t L, n, W, mode, rw;
+};
+// per-tile record counts and their exclusive scan base[0 .. L] (base[L] = all)
+hipError_t snap_count(const PackSrc& s, uint32_t* counts, uint64_t* base, hipStream_t st);
+// the records into out (room for cap records), tile by tile, in slot order
+hipError_t snap_pack(const PackSrc& s, const uint64_t* base, uint64_t cap, uint64_t* out, hipStream_t st);
+// n records back into their slots
+hipError_t snap_unpack(const PackSrc& s, const uint64_t* recs, uint64_t n, hipStream_t st);
 
 }  // namespace ggc

@@ -7,3 +7,10 @@
 // gg_coherent_begin does (nothing is reset or launched); *begun: a run has
 // been begun on it.  The pointers live as long as the context.
 gg_status gg_coh_launch_state(gg_ctx* ctx, const ggc::CP** P, const ggc::CS** S, bool* begun);
+
+// The trace's part of a snapshot (gg_coherent_snapshot / _restore): the
+// configuration of the run begun last, its header words and samples so far.
+gg_status gg_stats_snapshot(gg_ctx* ctx, std::vector<uint64_t>& words);
+bool      gg_stats_snapshot_ok(const gg_ctx* ctx, const uint64_t* w, uint64_t n);    // the words' shape (nothing changes)
+gg_status gg_stats_restore_configure(gg_ctx* ctx, const uint64_t* w);              // before gg_coherent_begin
+gg_status gg_stats_restore_upload(gg_ctx* ctx, const uint64_t* w, uint64_t n, hipStream_t s);   // after it

@@ -82,7 +82,7 @@ __global__ void __launch_bounds__(256) k_stats_scan(CP P, CS S, StatsDev D, uint
     if (S.qs[QS_START] != (uint64_t)L + 1) return;         // no quantum ended in this slot
     // quantum q ended, the run continues at quantum nq (qend_pick): the lax
     // barrier passes (q + 1) * Q ... nq * Q; the last quantum only its own
-    const uint64_t q = S.ri[GG_RI_FINAL_QUANTUM], nq = S.qs[QS_DONE] ? q + 1 : S.qs[QS_Q];
+    const uint64_t q = S.ri[GG_RI_FINAL_QUANTUM], nq = (S.qs[QS_DONE] & 3) ? q + 1 : S.qs[QS_Q];   // (a pause is no end)
     const uint64_t lo = (q + 1) * D.quantum_ns, hi = nq * D.quantum_ns;
     time_ns = (lo + D.interval_ns - 1) / D.interval_ns * D.interval_ns;
     if (time_ns > hi) return;
@@ -317,5 +317,50 @@ gg_status gg_stats_trace_dump(gg_ctx* ctx, int which, char* buf, uint64_t cap, u
   if (!buf || cap < *needed) return buf ? gg_fail(GG_ERR_RANGE, "statistics trace needs %llu bytes", (unsigned long long)*needed)
                                         : GG_OK;
   std::memcpy(buf, text.c_str(), text.size() + 1);
+  return GG_OK;
+}
+
+// ---- snapshot / restore of a run's trace (gg_coherent_snapshot):
+// {statistics, interval_ns, max_samples} of the run begun last, then, with a
+// trace on, the header words and the samples taken so far
+gg_status gg_stats_snapshot(gg_ctx* ctx, std::vector<uint64_t>& w)
+{
+  w.assign(3, 0);
+  const gg_stats_state* st = ctx->stats;
+  if (!st || !st->D.statistics) return GG_OK;
+  const StatsDev& D = st->D;
+  w[0] = D.statistics; w[1] = D.interval_ns; w[2] = D.max_samples;
+  w.resize(3 + SH_N);
+  GG_HIP(hipMemcpy(w.data() + 3, D.hdr, sizeof(uint64_t) * SH_N, hipMemcpyDeviceToHost));
+  const uint64_t n = std::min<uint64_t>(w[3 + SH_COUNT], D.max_samples) * D.stride;
+  w.resize(3 + SH_N + n);
+  if (n) GG_HIP(hipMemcpy(w.data() + 3 + SH_N, D.samples, sizeof(uint64_t) * n, hipMemcpyDeviceToHost));
+  return GG_OK;
+}
+// the words' shape against the context (nothing is changed)
+bool gg_stats_snapshot_ok(const gg_ctx* ctx, const uint64_t* w, uint64_t n)
+{
+  if (n < 3) return false;
+  if (w[0] == 0) return n == 3;
+  if (n < 3 + SH_N) return false;
+  const uint64_t stride = (uint64_t)GG_NUM_ST_FIELDS + ctx->cfg.num_tiles + 1, cnt = w[3 + SH_COUNT];
+  if (cnt > w[2] || w[2] > GG_ST_MAX_BUFFER_BYTES / (8 * stride)) return false;
+  return n == 3 + SH_N + cnt * stride;
+}
+// before gg_coherent_begin: the snapshot's trace becomes the context's
+gg_status gg_stats_restore_configure(gg_ctx* ctx, const uint64_t* w)
+{
+  if (w[0] == 0 && !ctx->stats) return GG_OK;
+  return gg_stats_trace_configure(ctx, (uint32_t)w[0], w[1], w[2]);
+}
+// after it: the header words and the samples
+gg_status gg_stats_restore_upload(gg_ctx* ctx, const uint64_t* w, uint64_t n, hipStream_t s)
+{
+  if (w[0] == 0) return GG_OK;
+  const StatsDev& D = ctx->stats->D;
+  GG_HIP(hipMemcpyAsync(D.hdr, w + 3, sizeof(uint64_t) * SH_N, hipMemcpyHostToDevice, s));
+  const uint64_t m = n - 3 - SH_N;
+  if (m) GG_HIP(hipMemcpyAsync(D.samples, w + 3 + SH_N, sizeof(uint64_t) * m, hipMemcpyHostToDevice, s));
+  GG_HIP(hipStreamSynchronize(s));
   return GG_OK;
 }

@@ -29,6 +29,12 @@
 //       and DIR/cache_line_replication.dat (gg_stats_trace_*; the interval
 //       defaults to the reference's 10000 ns; the run fails when it needs
 //       more than M samples, default 4096), sampled on the device
+//   gg_replay --coherent ... --checkpoint FILE --checkpoint-quantum Q
+//       runs until the quantum to run next is >= Q (gg_coherent_advance), writes
+//       the snapshot and the access words to FILE and exits 0, printing nothing
+//   gg_replay --coherent ... --restore FILE
+//       continues that run to its end (the same options as the first leg) and
+//       prints what the uninterrupted run prints
 //   gg_replay --stats-trace-selftest
 //       prints both files' text for a fixed three-sample input (no GPU needed)
 //   gg_replay --format-table FILE...
@@ -73,7 +79,8 @@ int main(int argc, char** argv)
   bool coherent = false, table = false, miss_types = false;
   uint32_t miss_lines = 0;
   uint64_t per_tile = 100000;
-  std::string trace, id_file, stats_dir;
+  std::string trace, id_file, stats_dir, ckpt_out, ckpt_in;
+  uint64_t ckpt_quantum = 0;
   uint64_t sampling_interval = 10000, max_samples = 4096;
   uint32_t protocol = GG_PROTO_MSI;
   int ranks = 1, rank = 0;
@@ -90,6 +97,9 @@ int main(int argc, char** argv)
     else if (a == "--miss-types") { miss_types = true; miss_lines = (uint32_t)std::strtoul(next(), nullptr, 0); }
     else if (a == "--coherent") coherent = true;
     else if (a == "--stats-trace") stats_dir = next();
+    else if (a == "--checkpoint") ckpt_out = next();
+    else if (a == "--checkpoint-quantum") ckpt_quantum = std::strtoull(next(), nullptr, 0);
+    else if (a == "--restore") ckpt_in = next();
     else if (a == "--sampling-interval") sampling_interval = std::strtoull(next(), nullptr, 0);
     else if (a == "--max-samples") max_samples = std::strtoull(next(), nullptr, 0);
     else if (a == "--protocol") {
@@ -235,6 +245,10 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "gg_replay: --stats-trace samples a single-process run\n");
         return 2;
       }
+      if ((!ckpt_out.empty() || !ckpt_in.empty()) && !id_file.empty()) {
+        std::fprintf(stderr, "gg_replay: --checkpoint / --restore are for a single-process run\n");
+        return 2;
+      }
       if (!id_file.empty()) {
         // one process per GPU: the RCCL communicator of `ranks` processes
         if (rank < 0 || rank >= ranks || shards % (uint32_t)ranks) {
@@ -279,7 +293,24 @@ int main(int argc, char** argv)
       if (!stats_dir.empty())
         check(gg_stats_trace_configure(be.ctx(), GG_ST_NETWORK_UTILIZATION | GG_ST_CACHE_LINE_REPLICATION, sampling_interval,
                                        max_samples), "gg_stats_trace_configure");
-      if (comm) check(gg_coherent_run_ranks(be.ctx(), comm, &tr, nullptr, nullptr), "gg_coherent_run_ranks");
+      if (!ckpt_out.empty() || !ckpt_in.empty()) {
+        // a run in legs: the access words travel with the snapshot
+        DeviceBuffer<uint64_t> words;
+        words.resize(n);
+        hip_check(hipMemset(words.p, 0, 8 * (n ? n : 1)), "hipMemset");
+        uint64_t nq = 0;
+        int done = 0;
+        if (!ckpt_in.empty()) readCheckpoint(ckpt_in, be, tr, words.p, n);
+        else check(gg_coherent_begin(be.ctx(), &tr, words.p, nullptr), "gg_coherent_begin");
+        check(gg_coherent_advance(be.ctx(), ckpt_out.empty() ? ~0ull : ckpt_quantum, &nq, &done), "gg_coherent_advance");
+        if (!ckpt_out.empty()) {
+          writeCheckpoint(ckpt_out, be, words.p, n);
+          std::fprintf(stderr, "gg_replay: %s at quantum %llu -> %s\n", done ? "run over" : "paused",
+                       (unsigned long long)nq, ckpt_out.c_str());
+          return 0;
+        }
+      }
+      else if (comm) check(gg_coherent_run_ranks(be.ctx(), comm, &tr, nullptr, nullptr), "gg_coherent_run_ranks");
       else check(gg_coherent_run(be.ctx(), &tr, nullptr, nullptr), "gg_coherent_run");
       std::vector<uint64_t> st((size_t)tiles * GG_NUM_TILE_STATS), cc((size_t)tiles * 2 * GG_NUM_CACHE_COUNTERS),
           nc((size_t)tiles * GG_NUM_NET_COUNTERS);

@@ -23,6 +23,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <fstream>
 #include <iomanip>
 #include <ostream>
 #include <queue>
@@ -683,6 +684,47 @@ struct DeviceBuffer {
   }
   ~DeviceBuffer() { if (p) hipFree(p); }
 };
+
+// ---- a coherent run in legs (gg_coherent_advance / _snapshot / _restore) ----
+// The checkpoint file of gg_replay --checkpoint / --restore: the snapshot and
+// the run's access words (the words of the records passed so far are final and
+// belong to the caller, so they travel beside the snapshot):
+//   {u64 snapshot bytes, u64 access words} snapshot, words
+inline void writeCheckpoint(const std::string& path, Backend& be, const uint64_t* access_dev, uint64_t words)
+{
+  uint64_t need = 0;
+  check(gg_coherent_snapshot_size(be.ctx(), &need), "gg_coherent_snapshot_size");
+  std::vector<uint8_t> blob(need);
+  check(gg_coherent_snapshot(be.ctx(), blob.data(), need, &need), "gg_coherent_snapshot");
+  std::vector<uint64_t> w(words);
+  if (words) hip_check(hipMemcpy(w.data(), access_dev, 8 * words, hipMemcpyDeviceToHost), "copy access words");
+  std::ofstream f(path, std::ios::binary);
+  const uint64_t hdr[2] = {need, words};
+  f.write(reinterpret_cast<const char*>(hdr), sizeof(hdr));
+  f.write(reinterpret_cast<const char*>(blob.data()), (std::streamsize)need);
+  f.write(reinterpret_cast<const char*>(w.data()), (std::streamsize)(8 * words));
+  f.close();
+  if (!f) throw Error(GG_ERR_INVALID, "cannot write " + path);
+}
+// the file back: the access words into access_dev (`words` of them), then gg_coherent_restore
+inline void readCheckpoint(const std::string& path, Backend& be, const gg_trace& tr, uint64_t* access_dev, uint64_t words)
+{
+  std::ifstream f(path, std::ios::binary);
+  uint64_t hdr[2] = {0, 0};
+  if (!f || !f.read(reinterpret_cast<char*>(hdr), sizeof(hdr))) throw Error(GG_ERR_INVALID, "cannot read " + path);
+  f.seekg(0, std::ios::end);
+  const uint64_t size = (uint64_t)f.tellg();
+  if (hdr[1] != words || hdr[0] > size || size - hdr[0] != sizeof(hdr) + 8 * words)
+    throw Error(GG_ERR_INVALID, path + ": not a checkpoint of this trace (sizes)");
+  f.seekg(sizeof(hdr));
+  std::vector<uint8_t> blob(hdr[0]);
+  std::vector<uint64_t> w(words);
+  f.read(reinterpret_cast<char*>(blob.data()), (std::streamsize)hdr[0]);
+  f.read(reinterpret_cast<char*>(w.data()), (std::streamsize)(8 * words));
+  if (!f) throw Error(GG_ERR_INVALID, "cannot read " + path);
+  if (words) hip_check(hipMemcpy(access_dev, w.data(), 8 * words, hipMemcpyHostToDevice), "copy access words");
+  check(gg_coherent_restore(be.ctx(), &tr, access_dev, blob.data(), blob.size(), nullptr), "gg_coherent_restore");
+}
 
 // Core::initiateMemoryAccess line split (core.cc:167-201): the line-aligned
 // addresses touched by [address, address + size), zero-size tail skipped.

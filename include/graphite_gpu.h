@@ -579,6 +579,57 @@ gg_status gg_coherent_run(gg_ctx* ctx, const gg_trace* trace, uint64_t* access_o
 #define GG_MANY_MAX 4096u
 gg_status gg_coherent_run_many(gg_ctx* const* ctxs, uint32_t n, const gg_trace* traces,
                                uint64_t* const* access_out_dev, gg_status* statuses, void* stream);
+/* A coherent run in legs: pause at a quantum boundary, snapshot, restore
+ * (DESIGN.md section 4i).
+ * gg_coherent_advance runs the device-driven loop of gg_coherent_run from the
+ * context's current state (after gg_coherent_begin or gg_coherent_restore, on
+ * a context that owns every shard; else GG_ERR_UNSUPPORTED) until the run is
+ * over (*done = 1; a deadlock: *done = 2 and gg_coherent_run's GG_ERR_STATE)
+ * or the quantum the device picked to run next is >= stop_quantum (*done = 0,
+ * *next_quantum = that quantum).  Quanta skipped as empty count: a stop
+ * inside a skipped span returns the first quantum chosen, which is larger.
+ * stop_quantum <= the current next quantum returns at once, with no launch
+ * and no change of state.  stop_quantum = ~0 never pauses: begin +
+ * advance(~0) is gg_coherent_run, bit for bit.  Traces with BARRIER records
+ * are accepted (a pending release is carried across the pause).  A leg with a
+ * finite stop takes the per-step launches on every mesh size; a leg with
+ * stop = ~0 takes what gg_coherent_run takes.  The results do not depend on
+ * where, or whether, a run was paused.  One begun run is driven either by
+ * gg_coherent_advance or by gg_coherent_quantum / gg_round_*: the other
+ * family returns GG_ERR_INVALID.  The getters (gg_coherent_get_stats,
+ * gg_noc_get_counters, gg_stats_trace_get, ...) work on a paused run.
+ *
+ * gg_coherent_snapshot copies everything the continuation depends on into
+ * host_buf: caches, directory and replaced entries with their sharer words,
+ * request FIFOs, DRAM and router queues, tile step state, statistics and
+ * counters, the quantum state, the record pools and lists as far as they are
+ * live, the error words and, when configured, the miss-type tables and the
+ * statistics trace with its configuration and samples.  The directory arrays
+ * and the miss-type tables are packed on the device to the slots in use.  It
+ * is valid at the device loop's clean point only: after gg_coherent_begin,
+ * after a gg_coherent_advance (paused or over) or gg_coherent_run, after a
+ * gg_coherent_restore; else GG_ERR_INVALID.  cap too small: GG_ERR_RANGE
+ * with *bytes = the need (gg_coherent_snapshot_size returns it alone).
+ * The trace and the access-word buffer are the caller's: words of records a
+ * tile has passed are final, gg_coherent_restore binds access_out_dev and
+ * writes only later records, so a caller who wants the whole array carries
+ * its buffer across.
+ * gg_coherent_restore resets the context as gg_coherent_begin does, then puts
+ * the state back (the snapshot's statistics-trace configuration included).
+ * The snapshot carries a format version, the gg_config bytes, the derived
+ * launch state (environment knobs included) and tile_offsets;
+ * GG_ERR_INVALID, with nothing changed and the context good for a fresh run,
+ * for a different config, launch state or tile_offsets, a truncated or
+ * corrupted buffer, a section past the buffer or of another size than the
+ * context's own.
+ * Not in scope: gg_coherent_run_many, the multi-rank round, a context that
+ * does not own every shard (GG_ERR_UNSUPPORTED), changing any setting
+ * across a restore.                                                         */
+gg_status gg_coherent_advance(gg_ctx* ctx, uint64_t stop_quantum, uint64_t* next_quantum, int* done);
+gg_status gg_coherent_snapshot_size(gg_ctx* ctx, uint64_t* bytes);
+gg_status gg_coherent_snapshot(gg_ctx* ctx, void* host_buf, uint64_t cap, uint64_t* bytes);
+gg_status gg_coherent_restore(gg_ctx* ctx, const gg_trace* trace, uint64_t* access_out_dev,
+                              const void* host_buf, uint64_t bytes, void* stream);
 /* The coherent mode over ranks (one process per GPU), RCCL over xGMI.
  * nccl_comm is an ncclComm_t (RCCL) of W ranks; rank r's context must own
  * logical shards [r*K/W, (r+1)*K/W) (cfg.shard_begin / shard_end, K =
