@@ -3595,16 +3595,28 @@ __device__ __forceinline__ void kt_end(const CS& S)
 //   (time, rank) order (sweep_positions);
 // * one wave per position (k_c_walk): the positions are served concurrently
 //   as a pipeline.  Wave w serves its port's pending packets in (time, rank)
-//   order; a packet is safe once its time is below the horizon of the wave
-//   before it: that wave's published lower bound on the time of any packet it
-//   will still serve, plus the router + link delay (a packet leaves a port no
-//   earlier than it arrived there, plus that delay).  Same requests, same
-//   order, at every port (pipeline_positions).
+//   order, as keys time << 12 | rank.  Its candidates are the packets whose
+//   route crosses its port and that it has not served; each has one moving
+//   word in LDS (time, position, status), stored by the wave that forwards
+//   it.  A candidate at this port is pending with its key.  A candidate still
+//   at an upstream position pp, with the time tt it arrived there, reaches
+//   this port no earlier than tt + d * zps (d ports in between, each adding
+//   the router + link delay zps and a queue delay >= 0): its bound key.  The
+//   least pending key is safe iff no upstream candidate's bound key is below
+//   it.
+//   Exact: a packet's key here is at least its bound key, ranks make keys
+//   unique, and words only move forward in time and position, so a stale
+//   read gives a smaller bound: it can delay a serve, never reorder one.
+//   Progress: of all unserved (packet, port) pairs take the least actual
+//   key; at its port every other candidate is pending or upstream with a
+//   larger key, hence a larger bound.  Same requests, same order, at every
+//   port as the sweep.  A wave with no candidate left is done; no other
+//   signal passes between the waves.
 // ---------------------------------------------------------------------------
-constexpr uint32_t kWalkSync = 512;                  // LDS: per-wave horizon / done words, run bounds
+constexpr uint32_t kWalkSync = 512;                  // LDS: run bounds, event count (diagnostics)
 constexpr uint32_t kMaxWalkWaves = 16;
 #ifndef GG_WALK_SLEEP
-#define GG_WALK_SLEEP 1                              // s_sleep units (64 cycles) between horizon polls
+#define GG_WALK_SLEEP 1                              // s_sleep units (64 cycles) between polls of the packet words
 #endif
 
 __device__ __forceinline__ uint64_t wave_min64(uint64_t v)
@@ -3613,13 +3625,13 @@ __device__ __forceinline__ uint64_t wave_min64(uint64_t v)
   for (int o = 32; o > 0; o >>= 1) { const uint64_t u = (uint64_t)__shfl_xor((long long)v, o); v = u < v ? u : v; }
   return v;
 }
-__device__ __forceinline__ uint64_t lds_load_acq(const uint64_t* p)
+__device__ __forceinline__ uint64_t lds_load_rlx(const uint64_t* p)
 {
-  return __hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
-__device__ __forceinline__ void lds_store_rel(uint64_t* p, uint64_t v)
+__device__ __forceinline__ void lds_store_rlx(uint64_t* p, uint64_t v)
 {
-  __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
 // the pipeline's packet word: time << 12 | position << 2 | status (times
@@ -3726,9 +3738,8 @@ __device__ __forceinline__ void walk_body(const CP& P, const CS& S, uint32_t L, 
   const uint64_t rq_qi = rq_direct ? (uint64_t)tile_at(dir ? sd.lo + wv : sd.hi - wv) * 6 + port : 0ull;
   uint8_t* qimg = smem;
   uint64_t* lc = reinterpret_cast<uint64_t*>(smem + (size_t)npos * P.qimg);     // [npos][kNetCtr]
-  uint64_t* wlow = lc + (size_t)npos * kNetCtr;                                  // [kMaxWalkWaves] horizons (kInf: done)
-  uint32_t* rlohi = reinterpret_cast<uint32_t*>(wlow + kMaxWalkWaves);           // lo, ~hi of the visited positions
-  uint8_t* pk = reinterpret_cast<uint8_t*>(wlow) + kWalkSync;
+  uint32_t* rlohi = reinterpret_cast<uint32_t*>(lc + (size_t)npos * kNetCtr);    // lo, ~hi of the visited positions
+  uint8_t* pk = reinterpret_cast<uint8_t*>(rlohi) + kWalkSync;
   if (n > P.walk_pk) { if (tid == 0) { atomicOr(S.err, GG_DERR_CAP); *cntp = 0; } return; }
   WalkLds W;
   W.Pt = reinterpret_cast<uint64_t*>(pk);
@@ -3798,7 +3809,6 @@ __device__ __forceinline__ void walk_body(const CP& P, const CS& S, uint32_t L, 
   if (!sweep)                     // the pipeline's moving state: one word per packet (W.Qt, unused by it)
     for (uint32_t i = tid; i < n; i += nthr) W.Qt[i] = pipe_word(W.Pt[i], W.Pp[i], 0u);
   for (uint32_t i = tid; i < npos * kNetCtr; i += nthr) lc[i] = 0;
-  for (uint32_t i = tid; i < kMaxWalkWaves; i += nthr) wlow[i] = 0;
   if (tid == 0) { rlohi[0] = ~0u; rlohi[1] = ~0u; rlohi[2] = 0; }
   __syncthreads();
   // canonical ranks (by send time, sender, seq); the positions the packets can visit
@@ -3911,6 +3921,7 @@ __device__ __forceinline__ void walk_body(const CP& P, const CS& S, uint32_t L, 
     HTree tr;
     if (visited && !direct) port_queue(pos, rq, tr);
     const uint32_t status_nx = (nx < sd.lo || nx > sd.hi) ? 2u : 0u;   // next router in another shard: held
+    const uint64_t zk = zps << 12;                                     // a port's router + link delay, in keys
     uint64_t cq = 0, cf = 0, m = 0;
     uint32_t spin = 0, polls = 0;
     const bool tev = DG(S.tre) && L >= kTrEv0 && L < kTrEv0 + S.tre_n;
@@ -3920,55 +3931,57 @@ __device__ __forceinline__ void walk_body(const CP& P, const CS& S, uint32_t L, 
       const uint32_t a = W.Pp[i], z = W.Pd[i];
       return dir ? (a <= pos && pos < z) : (a >= pos && pos > z);
     };
-    // per lane: its packets' rank, flits and exit position (fixed) in registers
+    // per lane: its candidates (the packets whose route crosses this port and
+    // that it has not served yet), their rank, flits and exit position (fixed)
+    // in registers
     bool c0 = visited && crosses(ln), c1 = visited && crosses(ln + 64);
     const uint32_t r0 = c0 ? W.Pr[ln] : 0u, r1 = c1 ? W.Pr[ln + 64] : 0u;
     const uint32_t fd0 = c0 ? (W.Pf[ln] & 0xFFFFFFu) | (W.Pd[ln] << 24) : 0u;   // flits (< 2^24) | exit pos << 24
     const uint32_t fd1 = c1 ? (W.Pf[ln + 64] & 0xFFFFFFu) | (W.Pd[ln + 64] << 24) : 0u;
-    uint64_t* wup = wv > 0 ? &wlow[wv - 1] : nullptr;
     // one loop exit, a readfirstlane'd flag: the loop is wave-uniform, so its
-    // carried values stay scalar (no exec-masked loop, no VGPR phis)
+    // carried scalars stay scalar (no exec-masked loop, no VGPR phis for them)
     uint32_t go = visited ? 1u : 0u;
-    uint64_t last_ul = 0;
+    uint64_t l0 = kInf, l1 = kInf;                    // the candidates' words at the last evaluation
     bool waiting = false;
     while (__builtin_amdgcn_readfirstlane((int)go)) {
-      // the horizon, in canonical keys (time << 12 | rank): the wave before
-      // publishes a lower bound on the key of every packet it will still
-      // serve (kInf once it has served its last one); such a packet reaches
-      // this port with a key at least that bound + zps << 12, so every
-      // pending packet with a key <= bound here is safe (keys are unique).
-      // A packet forwarded upstream with no queue delay is therefore safe at
-      // once, without waiting for the upstream port to move on.
-      uint64_t bound = kInf;
-      if (wup) {
-        const uint64_t ul = rq.rd64(lds_load_acq(wup));          // uniform (an atomic load is taken as divergent)
-        // a waiting wave re-evaluates only when the upstream word moved: every
-        // packet the wave before forwards comes with a new (larger) word, so
-        // an unchanged word means nothing new (the cheap poll keeps the
-        // waiting waves off the serving waves' issue slots)
-        if (waiting && ul == last_ul) {
-          if (++spin > (1u << 22)) { if (ln == 0) atomicOr(S.err, GG_DERR_STATE); go = 0; continue; }
-          __builtin_amdgcn_s_sleep(GG_WALK_SLEEP);
-          continue;
-        }
-        last_ul = ul;
-        bound = ul == kInf ? kInf : ul + (zps << 12);
+      // the candidates' packet words: the only signal between the waves (a
+      // forward is one relaxed atomic store of the word; nothing else travels
+      // with it).  A waiting wave re-evaluates only when one of them moved:
+      // its decision depends on nothing else (the cheap poll keeps the waiting
+      // waves off the serving waves' issue slots)
+      const uint64_t w0 = c0 ? lds_load_rlx(&W.Qt[ln]) : kInf;
+      const uint64_t w1 = c1 ? lds_load_rlx(&W.Qt[ln + 64]) : kInf;
+      if (waiting && !__ballot(w0 != l0 || w1 != l1)) {
+        if (++spin > (1u << 22)) { if (ln == 0) atomicOr(S.err, GG_DERR_STATE); go = 0; continue; }
+        __builtin_amdgcn_s_sleep(GG_WALK_SLEEP);
+        continue;
       }
       waiting = false;
-      const bool up_fin = bound == kInf;
-      // the least pending packet at this position, by (time, rank): each lane
-      // its least (the packet words, read after the acquire of the horizon
-      // word: every packet forwarded before that word was written is seen),
-      // then a scalar pass over the lanes holding one
-      const uint64_t w0 = c0 ? W.Qt[ln] : ~0ull;
-      const uint64_t w1 = c1 ? W.Qt[ln + 64] : ~0ull;
-      uint64_t mk = kInf;
+      l0 = w0; l1 = w1;
+      // per lane, in canonical keys (time << 12 | rank): the least key of its
+      // candidates pending here (mk), and the least bound key of those still
+      // upstream (bk): at position pp with time tt, d = |pos - pp| ports away,
+      // a packet arrives here no earlier than tt + d * zps (every port adds
+      // zps and a queue delay >= 0).  A stale word only gives a smaller bound.
+      uint64_t mk = kInf, bk = kInf;
       uint32_t mi = 0, mfd = 0;
-      if (pipe_pos(w0) == pos) { mk = (w0 & ~0xFFFull) | r0; mi = ln; mfd = fd0; }
-      if (pipe_pos(w1) == pos) {
-        const uint64_t k = (w1 & ~0xFFFull) | r1;
-        if (k < mk) { mk = k; mi = ln + 64; mfd = fd1; }
+      if (c0) {
+        const uint32_t pp = pipe_pos(w0);
+        const uint64_t k = (w0 & ~0xFFFull) | r0;
+        if (pp == pos) { mk = k; mi = ln; mfd = fd0; }
+        else bk = k + (uint64_t)(dir ? pos - pp : pp - pos) * zk;
       }
+      if (c1) {
+        const uint32_t pp = pipe_pos(w1);
+        const uint64_t k = (w1 & ~0xFFFull) | r1;
+        if (pp == pos) {
+          if (k < mk) { mk = k; mi = ln + 64; mfd = fd1; }
+        } else {
+          const uint64_t b = k + (uint64_t)(dir ? pos - pp : pp - pos) * zk;
+          bk = b < bk ? b : bk;
+        }
+      }
+      // the least pending key: a scalar pass over the lanes holding one
       uint64_t wk = kInf;
       uint32_t wl = 0;
       for (uint64_t bm = __ballot(mk != kInf); bm; bm &= bm - 1) {
@@ -3976,10 +3989,11 @@ __device__ __forceinline__ void walk_body(const CP& P, const CS& S, uint32_t L, 
         const uint64_t k = rl64(mk, l);
         if (k < wk) { wk = k; wl = l; }
       }
-      if (wk == kInf && up_fin) { go = 0; continue; }                   // nothing pending, nothing to come
-      if (wk > bound) {
-        // wait for upstream progress; publish the least key this port can still serve
-        if (ln == 0) lds_store_rel(&wlow[wv], wk < bound ? wk : bound);
+      // it is safe iff no candidate still upstream can arrive with a smaller
+      // key (keys are unique); no candidate left at all: this port is done
+      const uint64_t below = __ballot(bk < wk);
+      if (wk == kInf && !below) { go = 0; continue; }
+      if (below) {
         if (++spin > (1u << 22)) { if (ln == 0) atomicOr(S.err, GG_DERR_STATE); go = 0; continue; }
         ++polls;
         waiting = true;
@@ -3998,13 +4012,9 @@ __device__ __forceinline__ void walk_body(const CP& P, const CS& S, uint32_t L, 
       uint64_t evp = 0;
       auto pub = [&](uint64_t qd) {
         if (tev) evp = __builtin_amdgcn_s_memtime();
-        if (ln == 0) {
-          // the packet word (time, next position, status; the zero-load part,
-          // + zps per port, is added at the hand-off), then the horizon
-          // (release: the word is visible first)
-          W.Qt[i] = pipe_word(T + zps + lat_to_ps(qd, P.np.f), nx, status);
-          lds_store_rel(&wlow[wv], wk + 1);                   // every later key served here is > wk
-        }
+        // the forward: the packet word (time, next position, status; the
+        // zero-load part, + zps per port, is added at the hand-off)
+        if (ln == 0) lds_store_rlx(&W.Qt[i], pipe_word(T + zps + lat_to_ps(qd, P.np.f), nx, status));
       };
       uint64_t qd = 0;
       if (!qm) pub(0ull);
@@ -4027,7 +4037,6 @@ __device__ __forceinline__ void walk_body(const CP& P, const CS& S, uint32_t L, 
       }
       wave_sync();
     }
-    if (ln == 0) lds_store_rel(&wlow[wv], kInf);
     if (regq && visited && direct && m) {
       const uint64_t qi = (uint64_t)tile_at(pos) * 6 + port;
       rq.errp = S.err; rq.store(S.nq + qi, S.nnd + qi * P.np.max_size);
@@ -4141,6 +4150,8 @@ __device__ __forceinline__ void walk_body(const CP& P, const CS& S, uint32_t L, 
         atomicAdd(&DG(S.prof)[18], (unsigned long long)(e - _w2));
         atomicAdd(&DG(S.prof)[22], 1ull);
         atomicMax(&DG(S.prof)[1024 + 65536 + 2 * (L & 65535) + stage], (unsigned long long)(e - _p0));
+        atomicMax(&DG(S.prof)[46 + stage], (unsigned long long)n);         // the most packets one run held
+        if (PIPE && !sweep && n > 64) atomicAdd(&DG(S.prof)[48], 1ull);    // pipelined with second candidates
       }
       atomicMax(&DG(S.prof)[24 + stage], (unsigned long long)nev);
     }
