@@ -493,7 +493,9 @@ static gg_status coh_alloc(gg_ctx* ctx)
   } else entries = c.dir_total_entries;
   P.E = entries;
   const uint32_t dsets = entries / c.dir_assoc;
-  if (dsets == 0 || (dsets & (dsets - 1))) return gg_fail(GG_ERR_UNSUPPORTED, "directory sets must be a power of two");
+  // computeSetIndex folds floorLog2(sets)-bit fields (directory_cache.cc:64, 332-348): a set count that is no
+  // power of two uses its first 2^floorLog2 sets only; one set folds 0-bit fields and never ends in the reference
+  if (dsets < 2) return gg_fail(GG_ERR_UNSUPPORTED, "the directory needs at least two sets (dir_total_entries / dir_assoc)");
   P.log_dsets = (uint32_t)ilog2(dsets);
   P.log_slices = (uint32_t)clog2(slices);
   const uint64_t dir_size = (uint64_t)entries * (uint64_t)ceil(1.0 * P.T / 8);

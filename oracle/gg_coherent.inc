@@ -131,6 +131,10 @@ struct oracle_coh {
   uint64_t ri[GG_NUM_RUN_INFO];
   int err;
   int has_barrier, in_run;   /* BARRIER records in the trace; released by oracle_coh_run only */
+  /* oracle_coh_set_quantum_hook: called by oracle_coh_run when quantum q has
+   * ended and quantum nq runs next (nq = q + 1 after the last) */
+  void (*qhook)(void* arg, uint64_t q, uint64_t nq);
+  void* qhook_arg;
 };
 #define C_BAR_WAIT 2         /* c_tile.blocked of a tile waiting at a BARRIER record */
 
@@ -2053,6 +2057,7 @@ oracle_coh* oracle_coh_create(const gg_config* cfg)
   } else entries = cfg->dir_total_entries;
   C->dir_sets = entries / cfg->dir_assoc;
   C->log_dir_sets = (uint32_t)floor_log2(C->dir_sets);
+  if (C->dir_sets < 2) C->err = 1;               /* one set: computeSetIndex folds 0-bit fields and never ends */
   C->log_slices = (uint32_t)ceil_log2(slices);
   C->log_line = (uint32_t)floor_log2(cfg->line_size);
   uint32_t entry_bytes = (uint32_t)ceil(1.0 * C->T / 8);   /* DirectoryEntry::getSize(FULL_MAP) = app tiles bits */
@@ -2245,7 +2250,11 @@ int oracle_coh_run(oracle_coh* C, const uint64_t* addr, const uint32_t* meta,
     C->nbnd = 0;
     for (uint64_t i = 0; i < nb; ++i)                    /* the boundary exchange */
       if (c_accept(C, &C->bnd[i])) { C->in_run = 0; return GG_ERR_STATE; }
-    if (st[3] == 0 && nb == 0) break;            /* every trace finished, nothing in flight */
+    if (st[3] == 0 && nb == 0) {                 /* every trace finished, nothing in flight */
+      if (C->qhook) C->qhook(C->qhook_arg, q, q + 1);
+      break;
+    }
+    const uint64_t q_ended = q;
     uint64_t bw = 0, bmax = 0;                   /* tiles waiting at a BARRIER record, latest arrival */
     for (uint32_t i = 0; i < C->T; ++i) {
       const c_tile* Tl = &C->t[i];
@@ -2272,9 +2281,23 @@ int oracle_coh_run(oracle_coh* C, const uint64_t* addr, const uint32_t* meta,
     } else {
       q = q + 1;
     }
+    if (C->qhook) C->qhook(C->qhook_arg, q_ended, q);
   }
   C->in_run = 0;
   return C->err ? GG_ERR_STATE : 0;
+}
+
+/* A function oracle_coh_run calls between quanta: fn(arg, q, nq) when quantum
+ * q has ended (its boundary records handed over, a BARRIER released) and
+ * quantum nq runs next; after the last quantum nq = q + 1.  The state it may
+ * read (counters, oracle_coh_census) is that after quantum q's last step: the
+ * hand-over and the release change none of it.  NULL: none.  The series it
+ * gives is checked against the stepped run (begin / quantum / export /
+ * import) on traces without BARRIER records only: the stepped run takes no
+ * others (tests/test_replication_census.py). */
+void oracle_coh_set_quantum_hook(oracle_coh* C, void (*fn)(void*, uint64_t, uint64_t), void* arg)
+{
+  C->qhook = fn; C->qhook_arg = arg;
 }
 
 void oracle_coh_tile_stats(const oracle_coh* C, uint64_t* out)
@@ -2296,6 +2319,52 @@ void oracle_coh_cache_counters(const oracle_coh* C, uint64_t* out)
     memcpy(out + ((size_t)t * 2 + 0) * GG_NUM_CACHE_COUNTERS, C->t[t].c.l1.c, sizeof(uint64_t) * GG_NUM_CACHE_COUNTERS);
     memcpy(out + ((size_t)t * 2 + 1) * GG_NUM_CACHE_COUNTERS, C->t[t].c.l2.c, sizeof(uint64_t) * GG_NUM_CACHE_COUNTERS);
   }
+}
+
+/* The state cache_line_replication.dat is written from (…mosi/memory_manager.cc:
+ * 503-551), per tile, by walking the state itself:
+ *   lines[t]   = L1-D exclusive, L1-D shared, L2 exclusive, L2 shared lines of
+ *                tile t (MODIFIED; OWNED + SHARED, :530-535; no L1-I here);
+ *   hist[t][n] = entries of tile t's directory slice with n sharers, the
+ *                entries in _replaced_directory_entry_list included: what
+ *                Directory::updateSharerStats (directory.cc:55-79) keeps
+ *                incrementally for n >= 1 (an entry leaves the list only with
+ *                no sharer left).  n is the popcount of the sharer bit vector:
+ *                no count kept beside it is read.  Bin 0 (allocated entries
+ *                without a sharer) is no part of the reference's output;
+ *   pending[t] = entries of the replaced list that still have a sharer.
+ * Tiles of other shards stay zero.  Private-L2 protocols only. */
+int oracle_coh_census(const oracle_coh* C, uint64_t* lines, uint64_t* hist, uint64_t* pending)
+{
+  if (C->err) return GG_ERR_STATE;
+  if (C->shl2) return GG_ERR_UNSUPPORTED;
+  const uint32_t T = C->T, entries = C->dir_sets * C->dir_assoc;
+  memset(lines, 0, sizeof(uint64_t) * 4 * T);
+  memset(hist, 0, sizeof(uint64_t) * (size_t)T * (T + 1));
+  memset(pending, 0, sizeof(uint64_t) * T);
+  for (uint32_t t = 0; t < T; ++t) {
+    const c_tile* Tl = &C->t[t];
+    if (!c_owned(C, t)) continue;
+    const o_cache* lv[2] = { &Tl->c.l1, &Tl->c.l2 };
+    for (int k = 0; k < 2; ++k)
+      for (size_t i = 0; i < (size_t)lv[k]->sets * lv[k]->ways; ++i) {
+        const uint32_t cs = lv[k]->lines[i].cstate;
+        if (cs == GG_CSTATE_MODIFIED) lines[4 * t + 2 * k]++;
+        else if (cs == GG_CSTATE_SHARED || cs == GG_CSTATE_OWNED) lines[4 * t + 2 * k + 1]++;
+      }
+    uint64_t* h = hist + (size_t)t * (T + 1);
+    for (uint32_t i = 0; i < entries; ++i) {
+      const c_dentry* e = Tl->slot[i];
+      if (!e || e->addr == C_INVALID_ADDR) continue;
+      h[de_num(C, e)]++;
+    }
+    for (uint32_t i = 0; i < Tl->nreplaced; ++i) {
+      const uint32_t n = de_num(C, Tl->replaced[i]);
+      h[n]++;
+      if (n) pending[t]++;
+    }
+  }
+  return 0;
 }
 
 void oracle_coh_net_counters(const oracle_coh* C, uint64_t* out) { oracle_noc_counters(C->noc, out); }

@@ -113,6 +113,15 @@ void oracle_coh_run_info(const oracle_coh* C, uint64_t* out);        /* [GG_NUM_
 void oracle_coh_miss_types(const oracle_coh* C, uint64_t* out);      /* [tile][2][GG_NUM_MISS_TYPES] */
 void oracle_coh_proto_stats(const oracle_coh* C, uint64_t* out);     /* [tile][GG_NUM_PROTO_STATS] (MOSI) */
 void oracle_cache_miss_types(const oracle_cache* oc, uint64_t* out); /* [tile][2][GG_NUM_MISS_TYPES] */
+/* The state behind cache_line_replication.dat, by a walk (gg_coherent.inc):
+ * lines [T][4] = L1-D exclusive / shared, L2 exclusive / shared; hist
+ * [T][T+1] = directory entries (replaced list included) by popcount of their
+ * sharers; pending [T] = replaced entries that still have a sharer.
+ * GG_ERR_UNSUPPORTED under the shared-L2 protocols.                        */
+int  oracle_coh_census(const oracle_coh* C, uint64_t* lines, uint64_t* hist, uint64_t* pending);
+/* fn(arg, q, nq) from oracle_coh_run when quantum q has ended and quantum nq
+ * runs next (q + 1 after the last): runs with BARRIER records can be sampled */
+void oracle_coh_set_quantum_hook(oracle_coh* C, void (*fn)(void* arg, uint64_t q, uint64_t nq), void* arg);
 /* the whole run with one context per logical shard, `threads` OpenMP threads */
 /* tile-parallel steps on `threads` OpenMP threads (bit-identical results) */
 int  oracle_coh_set_threads(oracle_coh* C, int threads);

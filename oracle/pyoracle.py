@@ -28,6 +28,7 @@ def build(force=False):
     return LIB
 
 
+QUANTUM_HOOK = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64)
 _lib = None
 
 
@@ -109,6 +110,10 @@ def lib():
                   "oracle_coh_run_info", "oracle_coh_miss_types", "oracle_coh_proto_stats", "oracle_cache_miss_types"):
             getattr(L, n).argtypes = [vp, _u64p]
             getattr(L, n).restype = None
+        L.oracle_coh_set_quantum_hook.restype = None
+        L.oracle_coh_set_quantum_hook.argtypes = [vp, QUANTUM_HOOK, vp]
+        L.oracle_coh_census.restype = ctypes.c_int
+        L.oracle_coh_census.argtypes = [vp, _u64p, _u64p, _u64p]
         _lib = L
     return _lib
 
@@ -267,6 +272,25 @@ class OracleCoherent:
     def proto_stats(self):
         """MOSI event counters [tile][NUM_PROTO_STATS] (zeros under MSI)."""
         return self._get("oracle_coh_proto_stats", (self.cfg.num_tiles, 32))
+
+    def set_quantum_hook(self, fn):
+        """fn(q, nq) from run() when quantum q has ended and quantum nq runs
+        next (q + 1 after the last); None removes it."""
+        self._hook = QUANTUM_HOOK((lambda arg, q, nq: fn(int(q), int(nq))) if fn else 0)
+        lib().oracle_coh_set_quantum_hook(self.h, self._hook, None)
+
+    def census(self):
+        """The state behind cache_line_replication.dat by a walk of the caches
+        and the directory slices (oracle_coh_census): (lines [T][4] = L1-D
+        exclusive / shared, L2 exclusive / shared; hist [T][T+1] = directory
+        entries by popcount of their sharers, replaced list included; pending
+        [T] = replaced entries that still have a sharer)."""
+        T = self.cfg.num_tiles
+        lines, hist, pend = np.zeros((T, 4), np.uint64), np.zeros((T, T + 1), np.uint64), np.zeros(T, np.uint64)
+        rc = lib().oracle_coh_census(self.h, lines, hist, pend)
+        if rc != 0:
+            raise RuntimeError("coherent oracle census rc=%d" % rc)
+        return lines, hist, pend
 
 
 class OracleCache:

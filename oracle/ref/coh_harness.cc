@@ -37,7 +37,25 @@
 #include <map>
 #include <algorithm>
 #include <ucontext.h>
+#include <fstream>
+#include <iostream>
+#include <sstream>
+#include <set>
+#include <list>
+#include <queue>
+#include <cassert>
 
+// the census rows (coh_*_census.u64) walk the reference's CacheSet line infos
+// and the DirectoryCache's replaced-entry list, which are private members:
+// access widened for this translation unit only (the reference objects are
+// compiled as they are)
+#define private public
+#define protected public
+#include "cache_set.h"
+#include "cache.h"
+#include "directory_cache.h"
+#undef private
+#undef protected
 #include "tile.h"
 #include "config.h"
 #include "dvfs_manager.h"
@@ -346,11 +364,23 @@ Directory::Directory(CachingProtocolType cpt, DirectoryType dt, SInt32 total, SI
 {
   _directory_entry_list.resize(_total_entries);
   for (SInt32 i = 0; i < _total_entries; i++) _directory_entry_list[i] = DirectoryEntry::create(cpt, dt, hw, num);
+  if (_directory_type == FULL_MAP) initializeSharerStats();
 }
 Directory::~Directory() { for (SInt32 i = 0; i < _total_entries; i++) delete _directory_entry_list[i]; }
 DirectoryEntry* Directory::getDirectoryEntry(SInt32 n) { return _directory_entry_list[n]; }
 void Directory::setDirectoryEntry(SInt32 n, DirectoryEntry* e) { _directory_entry_list[n] = e; }
-void Directory::updateSharerStats(SInt32, SInt32) {}
+// the sharer statistics behind cache_line_replication.dat (directory.cc:47-80):
+// one bin per sharer count up to getTotalTiles(); an entry whose count changes
+// moves from its old bin to its new one, and entries without a sharer are not kept
+void Directory::initializeSharerStats() { _sharer_count_vec.assign(H.T + 3, 0); }
+void Directory::updateSharerStats(SInt32 from, SInt32 to)
+{
+  const SInt32 bins = (SInt32)_sharer_count_vec.size();
+  CHECK(_directory_type == FULL_MAP && from >= 0 && from < bins && to >= 0 && to < bins);
+  if (from) { CHECK(_sharer_count_vec[from] != 0); --_sharer_count_vec[from]; }
+  if (to) ++_sharer_count_vec[to];
+}
+void Directory::getSharerStats(vector<UInt64>& out) { out = _sharer_count_vec; }
 
 // ===========================================================================
 // DirectoryCache (cache/directory_cache.cc) — counters kept beside the object
@@ -903,6 +933,65 @@ static void run_app(UInt32 t)
   swapcontext(&here, &T.app_ctx);
 }
 
+#ifndef GG_PROTO_SHL2
+// The state behind cache_line_replication.dat (…mosi/memory_manager.cc:503-551)
+// after a quantum's last step, summed over the tiles: a row
+// [q, L1-D exclusive, L1-D shared, L2 exclusive, L2 shared, entries with 1 .. T sharers].
+// Lines: MODIFIED / OWNED + SHARED (:530-535) by a walk of the CacheSets' line
+// infos.  Entries: a walk of getNumSharers() over each slice's entries and its
+// _replaced_directory_entry_list; under MOSI the row holds what the
+// controller's own updateSharerStats calls (dram_directory_cntlr.cc:1029,1037)
+// left in Directory::_sharer_count_vec, which is what the reference prints,
+// and the walk is CHECKed against it.
+static vector<UInt64> g_census;
+static void count_lines(Cache* c, UInt64* ex, UInt64* sh)
+{
+  for (UInt32 s = 0; s < c->_num_sets; s++)
+    for (UInt32 w = 0; w < c->_associativity; w++) {
+      const CacheState::Type cs = c->_sets[s]->_cache_line_info_array[w]->getCState();
+      if (cs == CacheState::MODIFIED) (*ex)++;
+      else if (cs == CacheState::OWNED || cs == CacheState::SHARED) (*sh)++;
+    }
+}
+static void census_row(UInt64 q)
+{
+  vector<UInt64> row(5 + H.T, 0), walk(H.T + 1, 0);
+  row[0] = q;
+  for (UInt32 t = 0; t < H.T; ++t) {
+    MSI::MemoryManager* mm = g_t[t].mm;
+    count_lines(mm->getL1DCache(), &row[1], &row[2]);
+    count_lines(mm->getL2Cache(), &row[3], &row[4]);
+    DirectoryCache* dc = mm->getDramDirectoryCache();
+    Directory* d = dc->getDirectory();
+    for (UInt32 i = 0; i < dc->_total_entries; i++) {
+      DirectoryEntry* e = d->getDirectoryEntry(i);
+      if (e->getAddress() == INVALID_ADDRESS) continue;
+      const SInt32 n = e->getNumSharers();
+      CHECK(n >= 0 && n <= (SInt32)H.T);
+      walk[n]++;
+    }
+    for (size_t i = 0; i < dc->_replaced_directory_entry_list.size(); i++) {
+      const SInt32 n = dc->_replaced_directory_entry_list[i]->getNumSharers();
+      CHECK(n >= 0 && n <= (SInt32)H.T);
+      walk[n]++;
+    }
+#ifdef GG_PROTO_MOSI
+    vector<UInt64> inc;
+    d->getSharerStats(inc);
+    CHECK(inc.size() == H.T + 3);
+    for (UInt32 n = 1; n <= H.T; ++n) row[4 + n] += inc[n];
+    CHECK(inc[H.T + 1] == 0 && inc[H.T + 2] == 0);
+#endif
+  }
+#ifdef GG_PROTO_MOSI
+  for (UInt32 n = 1; n <= H.T; ++n) CHECK(row[4 + n] == walk[n]);
+#else
+  for (UInt32 n = 1; n <= H.T; ++n) row[4 + n] = walk[n];
+#endif
+  g_census.insert(g_census.end(), row.begin(), row.end());
+}
+#endif
+
 static int run_all(UInt64* quanta_out, UInt64* steps_out)
 {
   UInt64 q = 0, quanta = 0, steps = 0;
@@ -921,6 +1010,9 @@ static int run_all(UInt64* quanta_out, UInt64* steps_out)
       }
     }
     ++quanta;
+#ifndef GG_PROTO_SHL2
+    census_row(q);
+#endif
     size_t nb = g_bnd.size();
     for (size_t i = 0; i < nb; ++i) g_t[g_bnd[i].dst].inbox.push_back(g_bnd[i]);
     g_bnd.clear();
@@ -1027,6 +1119,9 @@ static void run_case(FILE* man, bool first, const char* name, UInt32 T, UInt32 N
   H.l2_assoc = l2_assoc; H.workload = workload; H.f = frequency;
   build_shard_map();
   g_t.clear(); g_t.resize(T); g_step.clear(); g_bnd.clear(); g_cc.clear(); g_dc.clear(); g_dram.clear();
+#ifndef GG_PROTO_SHL2
+  g_census.clear();
+#endif
   vector<UInt64> offs(T + 1);
   for (UInt32 t = 0; t <= T; ++t) offs[t] = raw ? raw->offs[t] : (UInt64)t * N;
   const size_t nrec = (size_t)offs[T];
@@ -1124,6 +1219,18 @@ static void run_case(FILE* man, bool first, const char* name, UInt32 T, UInt32 N
           workload == 2 ? "fft_real_p16_m10" : workload ? "stress" : "hotspot", (unsigned long long)nrec,
           (unsigned long long)quanta, (unsigned long long)steps);
   if (frequency != 1.0) fprintf(man, ", \"frequency_ghz\": %.17g", frequency);   // absent: 1.0
+#ifndef GG_PROTO_SHL2
+  {
+    // the census rows: the whole series when it is at most 256 KiB, else the last row
+    const size_t w = 5 + T;
+    size_t rows = g_census.size() / w;
+    CHECK(rows == quanta && rows > 0);
+    const UInt64* first_row = &g_census[0];
+    if (rows * w * 8 > 256 * 1024) { first_row += (rows - 1) * w; rows = 1; }
+    write_bin("coh_" + n + "_census.u64", first_row, rows * w * 8);
+    fprintf(man, ", \"census_rows\": %llu", (unsigned long long)rows);
+  }
+#endif
   fprintf(man, "}");
   printf("  coh %-10s tiles %u x %u: %llu quanta, %llu steps\n", name, T, N, (unsigned long long)quanta,
          (unsigned long long)steps);
@@ -1202,6 +1309,11 @@ int main(int argc, char** argv)
   run_case(man, false, "mosi_hot16f15", 16, 300, 8, 1, 1, 0, 16, 8, 0, NULL, 1.5);
   run_case(man, false, "mosi_hot12", 12, 300, 8, 1, 1, 0, 16);
   run_case(man, false, "mosi_shard72f266", 72, 100, 16, 8, 1, 0, 16, 8, 0, NULL, 2.66);
+  // mosi_dir16 in 4 shards: directory replacements whose NULLIFY crosses a
+  // quantum boundary (entries in the replaced list at the census)
+  run_case(man, false, "mosi_dir16s4", 16, 1000, 32, 4, 1, 64, 4);
+  // the same at half the length: the whole census series fits its file, rows with such entries included
+  run_case(man, false, "mosi_dir16s4n500", 16, 500, 32, 4, 1, 64, 4);
   if (argc > 2) {
     RawTrace fft;
     read_raw(string(argv[2]) + ".addr", fft.addr);
@@ -1242,6 +1354,11 @@ int main(int argc, char** argv)
   run_case(man, false, "hot16f15", 16, 300, 8, 1, 1, 0, 16, 8, 0, NULL, 1.5);
   run_case(man, false, "hot12", 12, 300, 8, 1, 1, 0, 16);
   run_case(man, false, "shard72f266", 72, 100, 16, 8, 1, 0, 16, 8, 0, NULL, 2.66);
+  // dir16 in 4 shards: directory replacements whose NULLIFY crosses a quantum
+  // boundary (entries in the replaced list at the census)
+  run_case(man, false, "dir16s4", 16, 1000, 32, 4, 1, 64, 4);
+  // the same at half the length: the whole census series fits its file, rows with such entries included
+  run_case(man, false, "dir16s4n500", 16, 500, 32, 4, 1, 64, 4);
   if (argc > 2) {
     RawTrace fft;
     read_raw(string(argv[2]) + ".addr", fft.addr);

@@ -157,3 +157,11 @@ def test_tile_parallel_oracle_equals_serial(T, K, net, hot):
     np.testing.assert_array_equal(par.cache_counters(), ref.cache_counters())
     np.testing.assert_array_equal(par.net_counters(), ref.net_counters())
     np.testing.assert_array_equal(par.run_info(), ref.run_info())
+
+
+def test_directory_of_one_set_is_refused():
+    """dir_total_entries == dir_assoc: computeSetIndex would fold 0-bit fields
+    without end (directory_cache.cc:332-348); the oracle refuses the run."""
+    a, m, o = po.gen_trace(16, 20, hot_lines=8)
+    with pytest.raises(RuntimeError):
+        po.OracleCoherent(C.default_config(16, dir_total_entries=4, dir_assoc=4)).run(a, m, o)

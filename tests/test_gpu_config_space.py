@@ -103,6 +103,35 @@ def test_small_caches_off_grid_clock():
     assert int(g[2][:, 1, C.CACHE_COUNTERS.index("evictions")].sum()) > 0
 
 
+@pytest.mark.parametrize("entries", [192, 24])
+@pytest.mark.parametrize("net", ["HC", "HBH"])
+def test_directory_sets_no_power_of_two(entries, net):
+    """48 and 6 directory sets of 4 ways: computeSetIndex folds
+    floorLog2(sets)-bit fields (directory_cache.cc:64, 332-348), so the first
+    32 / 4 sets are used; replacements occur."""
+    g = _run(N=600, hot=16, net_model=NETS[net], num_shards=4 if net == "HBH" else 1, l1d_size_kb=2, l2_size_kb=8,
+             dir_total_entries=entries, dir_assoc=4)
+    assert int(g[1][:, C.TILE_STATS.index("dir_evictions")].sum()) > 0
+
+
+def test_directory_of_one_set_is_refused():
+    """One set folds 0-bit fields: the reference's computeSetIndex never ends."""
+    from graphite_amd import backend as B
+    from oracle import pyoracle as po
+    torch = torch_dev()
+    a, m, o = po.gen_trace(16, 50, hot_lines=8)
+    cfg = C.default_config(16, dir_total_entries=4, dir_assoc=4)
+    be = B.Backend(cfg)
+    try:
+        with pytest.raises(B.GGError) as ei:                # the run's set-up refuses, not gg_create
+            be.coherent_run(to_dev(torch, a, torch.int64), to_dev(torch, m, torch.int32), o, None)
+    finally:
+        be.close()
+    assert ei.value.code == -3 and "two sets" in str(ei.value)
+    with pytest.raises(RuntimeError):                       # and so does the oracle
+        po.OracleCoherent(cfg).run(a, m, o)
+
+
 # ---- mesh shapes ---------------------------------------------------------------
 #  T     N   hot K(HBH)  other settings
 SHAPES = [

@@ -38,9 +38,12 @@ def _copy(hip, dst, src, nbytes):
         assert hip.hipMemcpy(ctypes.c_void_p(dst), ctypes.c_void_p(src), nbytes, 3) == 0   # hipMemcpyDeviceToDevice
 
 
-def _run_ranks(torch, W, K, cfg_kw, a, m, o, stats):
+def _run_ranks(torch, W, K, cfg_kw, a, m, o, stats, prepare=None, after_round=None):
     """The round protocol over W contexts with a device-copy transport;
-    returns (access words, tile stats, noc counters) summed over the ranks."""
+    returns (access words, tile stats, noc counters) summed over the ranks.
+    cfg_kw["config"]: further default_config fields.  prepare(be) before each
+    context's coherent_begin; after_round(bes, q, next_q, done) after every
+    finished round (quantum q ended on every rank, next_q runs next)."""
     from graphite_amd import backend as B
     from graphite_amd import coherent as CO
     hip = _hip()
@@ -50,8 +53,10 @@ def _run_ranks(torch, W, K, cfg_kw, a, m, o, stats):
     for r in range(W):
         k0, k1 = CO.shard_range(r, W, K)
         be = B.Backend(C.default_config(T, num_shards=K, shard_begin=k0, shard_end=k1, net_model=cfg_kw["net"],
-                                        protocol=cfg_kw.get("protocol", C.PROTO_MSI)))
+                                        protocol=cfg_kw.get("protocol", C.PROTO_MSI), **cfg_kw.get("config", {})))
         out = torch.zeros(len(a), dtype=torch.int64, device="cuda")
+        if prepare:
+            prepare(be)
         be.coherent_begin(addr, meta, o, out)
         bes.append(be); outs.append(out)
     rb = B.CMSG_RECORD_BYTES
@@ -91,6 +96,8 @@ def _run_ranks(torch, W, K, cfg_kw, a, m, o, stats):
             for r, be in enumerate(bes):
                 be.round_finish(ios[r])
         assert len({(io.next_q, io.done) for io in ios}) == 1
+        if after_round:
+            after_round(bes, q, ios[0].next_q, bool(ios[0].done))
         if ios[0].done:
             break
         q = ios[0].next_q

@@ -6,9 +6,10 @@ The expected network series comes from the oracle stepped quantum by quantum
 (begin / quantum / export / import_ with the next-quantum rule of
 oracle_coh_run), reading its network counters after every quantum: the
 oracle's stepped run equals its whole run, so the per-interval flit sums are
-the reference series.  The replication counts have no reference-compiled
-fixture ("parity unpinned"): they are checked against states known
-by construction and against protocol invariants."""
+the reference series.  The replication counts are checked here against states
+known by construction and against protocol invariants; sample by sample they
+are pinned to the oracle's census and to the census rows of the reference's
+own controllers in tests/test_gpu_replication.py."""
 import functools
 import os
 import subprocess
