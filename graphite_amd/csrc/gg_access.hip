@@ -167,41 +167,36 @@ gg_status gg_split_accesses(const uint64_t* addr_dev, const uint32_t* size_dev, 
   const uint64_t nb = (n + kScanBlock - 1) / kScanBlock;
   uint64_t *cnt = nullptr, *bsum = nullptr, *toff = nullptr, *total = nullptr;
   uint32_t* err = nullptr;
-  gg_status st = GG_OK;
-  auto run = [&]() -> gg_status {
-    GG_HIP(hipMalloc((void**)&cnt, sizeof(uint64_t) * n));
-    GG_HIP(hipMalloc((void**)&bsum, sizeof(uint64_t) * nb));
-    GG_HIP(hipMalloc((void**)&toff, sizeof(uint64_t) * (tiles + 1)));
-    GG_HIP(hipMalloc((void**)&total, sizeof(uint64_t)));
-    GG_HIP(hipMalloc((void**)&err, sizeof(uint32_t)));
-    GG_HIP(hipMemcpyAsync(toff, tile_offsets, sizeof(uint64_t) * (tiles + 1), hipMemcpyHostToDevice, s));
-    GG_HIP(hipMemsetAsync(err, 0, sizeof(uint32_t), s));
-    hipLaunchKernelGGL(k_split_count, dim3((uint32_t)nb), dim3(kScanBlock), 0, s, addr_dev, size_dev, n, line_size, cnt, bsum);
-    GG_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(kScanBlock), 0, s, bsum, nb, total);
-    GG_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_split_write, dim3((uint32_t)nb), dim3(kScanBlock), 0, s, addr_dev, size_dev, meta_dev, n,
-                       line_size, cnt, bsum, toff, tiles, first_dev, line_addr_dev, line_meta_dev, cap, err);
-    GG_HIP(hipGetLastError());
-    uint32_t e = 0;
-    GG_HIP(hipMemcpyAsync(num_lines, total, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    GG_HIP(hipMemcpyAsync(&e, err, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    if (line_tile_offsets)
-      for (uint32_t t = 0; t <= tiles; ++t)
-        GG_HIP(hipMemcpyAsync(&line_tile_offsets[t], first_dev + tile_offsets[t], sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    GG_HIP(hipStreamSynchronize(s));
-    if (e & GG_DERR_BARRIER)
-      return gg_fail(GG_ERR_UNSUPPORTED, "gg_split_accesses: a BARRIER record in the access trace (insert barriers "
-                     "into the line records after the split)");
-    if (e) return gg_fail(GG_ERR_INVALID, "gg_split_accesses: carried gap above 2^30 cycles");
-    if (line_addr_dev && *num_lines > cap)
-      return gg_fail(GG_ERR_INVALID, "gg_split_accesses: %llu lines, capacity %llu", (unsigned long long)*num_lines,
-                     (unsigned long long)cap);
-    return GG_OK;
-  };
-  st = run();
-  for (void* p : {(void*)cnt, (void*)bsum, (void*)toff, (void*)total, (void*)err}) if (p) hipFree(p);
-  return st;
+  gg_arena tmp;                                  // freed on every way out
+  if (gg_status st = tmp.alloc(&cnt, n)) return st;
+  if (gg_status st = tmp.alloc(&bsum, nb)) return st;
+  if (gg_status st = tmp.alloc(&toff, (uint64_t)tiles + 1)) return st;
+  if (gg_status st = tmp.alloc(&total, 1)) return st;
+  if (gg_status st = tmp.alloc(&err, 1)) return st;
+  GG_HIP(hipMemcpyAsync(toff, tile_offsets, sizeof(uint64_t) * (tiles + 1), hipMemcpyHostToDevice, s));
+  GG_HIP(hipMemsetAsync(err, 0, sizeof(uint32_t), s));
+  hipLaunchKernelGGL(k_split_count, dim3((uint32_t)nb), dim3(kScanBlock), 0, s, addr_dev, size_dev, n, line_size, cnt, bsum);
+  GG_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(kScanBlock), 0, s, bsum, nb, total);
+  GG_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_split_write, dim3((uint32_t)nb), dim3(kScanBlock), 0, s, addr_dev, size_dev, meta_dev, n,
+                     line_size, cnt, bsum, toff, tiles, first_dev, line_addr_dev, line_meta_dev, cap, err);
+  GG_HIP(hipGetLastError());
+  uint32_t e = 0;
+  GG_HIP(hipMemcpyAsync(num_lines, total, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  GG_HIP(hipMemcpyAsync(&e, err, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  if (line_tile_offsets)
+    for (uint32_t t = 0; t <= tiles; ++t)
+      GG_HIP(hipMemcpyAsync(&line_tile_offsets[t], first_dev + tile_offsets[t], sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  GG_HIP(hipStreamSynchronize(s));
+  if (e & GG_DERR_BARRIER)
+    return gg_fail(GG_ERR_UNSUPPORTED, "gg_split_accesses: a BARRIER record in the access trace (insert barriers "
+                   "into the line records after the split)");
+  if (e) return gg_fail(GG_ERR_INVALID, "gg_split_accesses: carried gap above 2^30 cycles");
+  if (line_addr_dev && *num_lines > cap)
+    return gg_fail(GG_ERR_INVALID, "gg_split_accesses: %llu lines, capacity %llu", (unsigned long long)*num_lines,
+                   (unsigned long long)cap);
+  return GG_OK;
 }
 
 gg_status gg_combine_accesses(const uint64_t* line_out_dev, const uint64_t* first_dev, uint64_t n,

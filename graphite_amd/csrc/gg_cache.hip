@@ -2019,17 +2019,6 @@ size_t replay_lds_bytes(const gg_geom& g, bool lean)
          (g.pol2 == GG_POLICY_LRU ? 0 : (size_t)g.s2 * GG_WAVE);
 }
 
-template <class T>
-gg_status grow(T** p, uint64_t* cap, uint64_t need)
-{
-  if (need <= *cap && *p) return GG_OK;
-  if (*p) { hipFree(*p); *p = nullptr; }
-  uint64_t n = std::max<uint64_t>(need, 1) + need / 8;
-  GG_HIP(hipMalloc((void**)p, n * sizeof(T)));
-  *cap = n;
-  return GG_OK;
-}
-
 }  // namespace
 
 gg_status gg_cache_state_alloc(gg_ctx* ctx)
@@ -2041,28 +2030,19 @@ gg_status gg_cache_state_alloc(gg_ctx* ctx)
                    g.a1, g.a2, g.pol1, g.pol2);
   if (replay_lds_bytes(g, false) > 64 * 1024)
     return gg_fail(GG_ERR_UNSUPPORTED, "L2 lines per L1-D set (%u) too large for the LDS-resident replay", g.s2 * g.a2);
-  GG_HIP(hipMalloc((void**)&cs.l1_tag, sizeof(uint64_t) * g.a1 * g.units));
-  GG_HIP(hipMalloc((void**)&cs.l1_meta, sizeof(uint64_t) * g.units));
-  GG_HIP(hipMalloc((void**)&cs.l1_rr, g.units));
-  GG_HIP(hipMalloc((void**)&cs.l2_tag, sizeof(uint32_t) * g.s2 * g.a2 * g.units));
-  GG_HIP(hipMalloc((void**)&cs.l2_meta, sizeof(uint64_t) * g.s2 * g.mw * g.units));
-  GG_HIP(hipMalloc((void**)&cs.l2_rr, (size_t)g.s2 * g.units));
-  GG_HIP(hipMalloc((void**)&cs.counters, sizeof(uint64_t) * g.tiles * 2 * GG_NUM_CACHE_COUNTERS));
-  GG_HIP(hipMalloc((void**)&ctx->unit_len, sizeof(uint32_t) * g.units));
-  GG_HIP(hipMalloc((void**)&ctx->unit_base, sizeof(uint64_t) * g.units));
-  GG_HIP(hipMalloc((void**)&ctx->total_dev, sizeof(uint64_t)));
-  GG_HIP(hipMalloc((void**)&ctx->tile_off_dev, sizeof(uint64_t) * (g.tiles + 1)));
-  return GG_OK;
-}
-
-void gg_cache_state_free(gg_ctx* ctx)
-{
-  gg_cache_state& cs = ctx->cs;
-  void* ps[] = {cs.l1_tag, cs.l1_meta, cs.l1_rr, cs.l2_tag, cs.l2_meta, cs.l2_rr, cs.counters,
-                ctx->sh_key, ctx->sh_res, ctx->sh_ev, ctx->rec_slot, ctx->chunk_cnt, ctx->chunk_tile, ctx->chunk_start,
-                ctx->chunk_len, ctx->unit_len, ctx->unit_base, ctx->tile_off_dev, ctx->total_dev,
-                ctx->mt.tab, ctx->mt.cnt};
-  for (void* p : ps) if (p) hipFree(p);
+  gg_arena& m = ctx->mem;
+  gg_status st = m.alloc(&cs.l1_tag, (uint64_t)g.a1 * g.units);
+  if (!st) st = m.alloc(&cs.l1_meta, g.units);
+  if (!st) st = m.alloc(&cs.l1_rr, g.units);
+  if (!st) st = m.alloc(&cs.l2_tag, (uint64_t)g.s2 * g.a2 * g.units);
+  if (!st) st = m.alloc(&cs.l2_meta, (uint64_t)g.s2 * g.mw * g.units);
+  if (!st) st = m.alloc(&cs.l2_rr, (uint64_t)g.s2 * g.units);
+  if (!st) st = m.alloc(&cs.counters, (uint64_t)g.tiles * 2 * GG_NUM_CACHE_COUNTERS);
+  if (!st) st = m.alloc(&ctx->unit_len, g.units);
+  if (!st) st = m.alloc(&ctx->unit_base, g.units);
+  if (!st) st = m.alloc(&ctx->total_dev, 1);
+  if (!st) st = m.alloc(&ctx->tile_off_dev, (uint64_t)g.tiles + 1);
+  return st;
 }
 
 // gg_cache_track_miss_types after its checks: the address table (every word
@@ -2076,13 +2056,17 @@ gg_status gg_cache_mt_alloc(gg_ctx* ctx, uint64_t lines)
   v.log_spu = (uint32_t)__builtin_ctzll(lines) - g.log_u1;
   const size_t bytes = (size_t)g.tiles * (v.on1 + v.on2) * lines * sizeof(uint64_t);
   const size_t cbytes = sizeof(unsigned long long) * g.tiles * 2 * GG_NUM_MISS_TYPES;
-  GG_HIP(hipMalloc((void**)&v.tab, bytes));
-  if (hipError_t e = hipMalloc((void**)&v.cnt, cbytes)) { hipFree(v.tab); return gg_hip_check(e, "hipMalloc(miss types)"); }
+  gg_dbuf<uint64_t> tab;
+  gg_dbuf<unsigned long long> cnt;
+  if (gg_status st = tab.reserve(bytes / sizeof(uint64_t))) return st;
+  if (gg_status st = cnt.reserve(cbytes / sizeof(unsigned long long))) return st;
+  v.tab = tab.get(); v.cnt = cnt.get();
   hipStream_t s = ctx->last_stream;
   GG_HIP(hipMemsetAsync(v.tab, 0xFF, bytes, s));
   GG_HIP(hipMemsetAsync(v.cnt, 0, cbytes, s));
   GG_HIP(hipStreamSynchronize(s));
-  if (ctx->mt.tab) { hipFree(ctx->mt.tab); hipFree(ctx->mt.cnt); }   // a fresh context sized again
+  ctx->mt_tab = std::move(tab);           // (a fresh context sized again: the old pair is freed here)
+  ctx->mt_cnt = std::move(cnt);
   ctx->mt = v;
   ctx->mt_lines = lines;
   return GG_OK;
@@ -2145,9 +2129,9 @@ gg_status gg_cache_run_batch(gg_ctx* ctx, const gg_trace* tr, uint32_t* result, 
       static const int dbg_on = getenv("GG_STREAM_DEBUG") ? atoi(getenv("GG_STREAM_DEBUG")) : 0;
       const char* bi = getenv("GG_STREAM_BAD_INDEX");
       const bool bad_index = bi && atoi(bi) == 1;
-      unsigned long long* dbg = nullptr;
+      gg_dbuf<unsigned long long> dbg;
       if (dbg_on || bad_index) {
-        GG_HIP(hipMalloc((void**)&dbg, 8 * sizeof(unsigned long long)));
+        if (gg_status st = dbg.reserve(8)) return st;
         GG_HIP(hipMemsetAsync(dbg, 0, 8 * sizeof(unsigned long long), s));
         if (dbg_on == 2) GG_HIP(hipMemsetAsync(dbg + 7, 1, 1, s));   // GG_STREAM_DEBUG=2: skip the cache step (builds with -DGG_STREAM_NOSTEP)
         if (bad_index) GG_HIP(hipMemsetAsync(dbg + 6, 1, 1, s));
@@ -2155,18 +2139,18 @@ gg_status gg_cache_run_batch(gg_ctx* ctx, const gg_trace* tr, uint32_t* result, 
       if (sk)
         hipLaunchKernelGGL(fn, dim3(g.tiles), dim3((ncw + 1) * GG_WAVE), lds, s, ctx->cs, g, tr->addr_dev,
                            tr->meta_dev, (const uint64_t*)ctx->tile_off_dev, result, evicted,
-                           ctx->err_dev, dbg, MtArg<false>{});
+                           ctx->err_dev, dbg.get(), MtArg<false>{});
       else
         hipLaunchKernelGGL(fn_mt, dim3(g.tiles), dim3((ncw + 1) * GG_WAVE), lds, s, ctx->cs, g, tr->addr_dev,
                            tr->meta_dev, (const uint64_t*)ctx->tile_off_dev, result, evicted,
-                           ctx->err_dev, dbg, MtArg<true>{ctx->mt, ctx->err_dev});
+                           ctx->err_dev, dbg.get(), MtArg<true>{ctx->mt, ctx->err_dev});
       GG_HIP(hipGetLastError());
       gg_timer_end(ctx, "cache_stream", s);
       if (dbg) {
         unsigned long long h[8];
         GG_HIP(hipMemcpyAsync(h, dbg, sizeof(h), hipMemcpyDeviceToHost, s));
         GG_HIP(hipStreamSynchronize(s));
-        hipFree(dbg);
+        dbg.reset();
         if (dbg_on) fprintf(stderr, "[gg_stream] batches %llu slow %llu producer-spins %llu | consumer wave-iters %llu "
                 "idle-sleeps %llu records %llu (lane util %.3f)\n", h[0], h[1], h[2], h[3], h[4], h[5],
                 h[3] ? (double)h[5] / (64.0 * h[3]) : 0.0);
@@ -2191,14 +2175,10 @@ gg_status gg_cache_run_batch(gg_ctx* ctx, const gg_trace* tr, uint32_t* result, 
   tile_chunk0[g.tiles] = (uint32_t)ctx->h_chunk_tile.size();
   const uint64_t nchunks = ctx->h_chunk_tile.size();
   const uint64_t n = tr->num_records;
-  if (nchunks + 2 * (g.tiles + 1) > ctx->chunk_cap || !ctx->chunk_tile) {
-    uint64_t cap = (nchunks + 2 * (g.tiles + 1)) * 2 + 64;
-    if (ctx->chunk_cnt) { hipFree(ctx->chunk_cnt); hipFree(ctx->chunk_tile); hipFree(ctx->chunk_start); hipFree(ctx->chunk_len); }
-    GG_HIP(hipMalloc((void**)&ctx->chunk_cnt, sizeof(uint32_t) * cap * g.u1));
-    GG_HIP(hipMalloc((void**)&ctx->chunk_tile, sizeof(uint32_t) * cap));
-    GG_HIP(hipMalloc((void**)&ctx->chunk_start, sizeof(uint64_t) * cap));
-    GG_HIP(hipMalloc((void**)&ctx->chunk_len, sizeof(uint32_t) * cap));
-    ctx->chunk_cap = cap;
+  {
+    const uint64_t need = nchunks + 2 * (g.tiles + 1), cap = need * 2 + 64;
+    if (gg_status st = ctx->chunk_cnt.reserve(need * g.u1, cap * g.u1)) return st;
+    if (gg_status st = gg_reserve_all(need, cap, ctx->chunk_tile, ctx->chunk_start, ctx->chunk_len)) return st;
   }
   // upload tables (chunk_tile doubles as storage for tile_chunk0 after the chunk entries)
   GG_HIP(hipMemcpyAsync(ctx->chunk_tile, ctx->h_chunk_tile.data(), sizeof(uint32_t) * nchunks, hipMemcpyHostToDevice, s));
@@ -2226,10 +2206,12 @@ gg_status gg_cache_run_batch(gg_ctx* ctx, const gg_trace* tr, uint32_t* result, 
   GG_HIP(hipMemcpyAsync(&total, ctx->total_dev, sizeof(total), hipMemcpyDeviceToHost, s));
   GG_HIP(hipStreamSynchronize(s));
   if (total >= (1ull << 32)) return gg_fail(GG_ERR_RANGE, "batch needs %llu record slots (limit 2^32)", (unsigned long long)total);
-  if (gg_status st = grow(&ctx->sh_key, &ctx->sh_cap, total)) return st;
-  if (gg_status st = grow(&ctx->rec_slot, &ctx->rec_cap, n)) return st;
-  if (result) { if (gg_status st = grow(&ctx->sh_res, &ctx->sh_res_cap, total)) return st; }
-  if (evicted) { if (gg_status st = grow(&ctx->sh_ev, &ctx->sh_ev_cap, total)) return st; }
+  // (at least one element each, with an eighth to spare)
+  auto grow = [](auto& b, uint64_t need) { return b.reserve(std::max<uint64_t>(need, 1), std::max<uint64_t>(need, 1) + need / 8); };
+  if (gg_status st = grow(ctx->sh_key, total)) return st;
+  if (gg_status st = grow(ctx->rec_slot, n)) return st;
+  if (result) { if (gg_status st = grow(ctx->sh_res, total)) return st; }
+  if (evicted) { if (gg_status st = grow(ctx->sh_ev, total)) return st; }
   if (nchunks) {
     gg_timer_begin(ctx, "cache_scatter", s);
     // persistent: 8 one-wave workgroups per CU, a multiple of 8 (measured
@@ -2256,16 +2238,16 @@ gg_status gg_cache_run_batch(gg_ctx* ctx, const gg_trace* tr, uint32_t* result, 
   if (ctx->mt.tab)
     hipLaunchKernelGGL(k->replay_mt, dim3(groups), dim3(GG_WAVE), replay_lds_bytes(g, false), s, ctx->cs, g,
                        (const uint64_t*)ctx->sh_key, (const uint32_t*)ctx->unit_len, (const uint64_t*)ctx->unit_base,
-                       result ? ctx->sh_res : nullptr, evicted ? ctx->sh_ev : nullptr, ctx->err_dev,
+                       result ? ctx->sh_res.get() : nullptr, evicted ? ctx->sh_ev.get() : nullptr, ctx->err_dev,
                        MtArg<true>{ctx->mt, ctx->err_dev});
   else if (lean)
     hipLaunchKernelGGL(lean->replay, dim3(groups), dim3(GG_WAVE), replay_lds_bytes(g, true), s, ctx->cs, g,
                        (const uint64_t*)ctx->sh_key, (const uint32_t*)ctx->unit_len, (const uint64_t*)ctx->unit_base,
-                       result ? ctx->sh_res : nullptr, evicted ? ctx->sh_ev : nullptr, ctx->err_dev);
+                       result ? ctx->sh_res.get() : nullptr, evicted ? ctx->sh_ev.get() : nullptr, ctx->err_dev);
   else
     hipLaunchKernelGGL(k->replay, dim3(groups), dim3(GG_WAVE), replay_lds_bytes(g, false), s, ctx->cs, g,
                        (const uint64_t*)ctx->sh_key, (const uint32_t*)ctx->unit_len, (const uint64_t*)ctx->unit_base,
-                       result ? ctx->sh_res : nullptr, evicted ? ctx->sh_ev : nullptr, ctx->err_dev, MtArg<false>{});
+                       result ? ctx->sh_res.get() : nullptr, evicted ? ctx->sh_ev.get() : nullptr, ctx->err_dev, MtArg<false>{});
   GG_HIP(hipGetLastError());
   gg_timer_end(ctx, "cache_replay", s);
   if (n && (result || evicted)) {
@@ -2290,20 +2272,20 @@ gg_status gg_cache_quartet(gg_ctx* ctx, int op, uint32_t tile, int level, uint64
   q.op = op; q.level = level; q.tile = tile; q.addr = addr;
   if (in) q.in = *in;
   if (out) q.out = *out; else { q.out.tag = ~0ull; q.out.cstate = 0; q.out.cached_loc = 0; }
-  QuartetIO* d = nullptr;
-  GG_HIP(hipMalloc((void**)&d, sizeof(QuartetIO)));
+  gg_dbuf<QuartetIO> d;
+  if (gg_status st = d.reserve(1)) return st;
   hipStream_t s = ctx->last_stream;
   GG_HIP(hipMemcpyAsync(d, &q, sizeof(q), hipMemcpyHostToDevice, s));
   ctx->cache_dirty = true;
   const Kern* k = find_kernel(g.a1, g.a2, g.pol1, g.pol2);
   if (ctx->mt.tab)
-    hipLaunchKernelGGL(k->quartet_mt, dim3(1), dim3(1), 0, s, ctx->cs, g, d, MtArg<true>{ctx->mt, ctx->err_dev});
+    hipLaunchKernelGGL(k->quartet_mt, dim3(1), dim3(1), 0, s, ctx->cs, g, d.get(), MtArg<true>{ctx->mt, ctx->err_dev});
   else
-    hipLaunchKernelGGL(k->quartet, dim3(1), dim3(1), 0, s, ctx->cs, g, d, MtArg<false>{});
+    hipLaunchKernelGGL(k->quartet, dim3(1), dim3(1), 0, s, ctx->cs, g, d.get(), MtArg<false>{});
   GG_HIP(hipGetLastError());
   GG_HIP(hipMemcpyAsync(&q, d, sizeof(q), hipMemcpyDeviceToHost, s));
   GG_HIP(hipStreamSynchronize(s));
-  hipFree(d);
+  d.reset();
   if (out) *out = q.out;
   if (eviction) *eviction = q.eviction;
   if (ev_addr) *ev_addr = q.ev_addr;

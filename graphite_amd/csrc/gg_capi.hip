@@ -206,10 +206,7 @@ gg_ctx* gg_create(const gg_config* cfg, gg_status* status)
 
   gg_status st = gg_cache_state_alloc(ctx);
   if (st == GG_OK) st = gg_noc_alloc(ctx);
-  if (st == GG_OK) {
-    he = hipMalloc((void**)&ctx->err_dev, 2 * sizeof(uint32_t));   // flags, first failing source line (coherent)
-    if (he != hipSuccess) st = gg_hip_check(he, "hipMalloc(err)");
-  }
+  if (st == GG_OK) st = ctx->mem.alloc(&ctx->err_dev, 2);   // flags, first failing source line (coherent)
   if (st == GG_OK) st = gg_reset(ctx);
   if (st != GG_OK) { gg_destroy(ctx); *status = st; return nullptr; }
   *status = GG_OK;
@@ -221,15 +218,12 @@ void gg_destroy(gg_ctx* ctx)
   if (!ctx) return;
   hipSetDevice(ctx->device);
   hipDeviceSynchronize();
-  gg_cache_state_free(ctx);
   gg_noc_free(ctx);
   gg_coh_free(ctx);
-  gg_core_free(ctx);
   gg_stats_free(ctx);
   if (ctx->round && ctx->round_free) ctx->round_free(ctx->round);
-  if (ctx->err_dev) hipFree(ctx->err_dev);
   for (gg_timer& t : ctx->timers) { hipEventDestroy(t.start); hipEventDestroy(t.stop); }
-  delete ctx;
+  delete ctx;             // the context's own arrays: its arena and buffers (gg_devmem.h)
 }
 
 gg_status gg_reset(gg_ctx* ctx)

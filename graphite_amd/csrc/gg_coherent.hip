@@ -240,7 +240,7 @@ struct gg_coh_state {
   CS S{};
   CP* Pd = nullptr;                  // device copies of P / S (k_c_step reads its launch state through them)
   CS* Sd = nullptr;
-  std::vector<void*> allocs;
+  gg_arena mem;                      // owns every array of the state but the three buffers below
   uint64_t* status_dev = nullptr;
   uint32_t* ecount_dev = nullptr;    // export counts + cursors
   uint64_t* offs_dev = nullptr;
@@ -264,13 +264,11 @@ struct gg_coh_state {
   // packing scratch of a snapshot (gg_snapshot.hip): per-tile counts, their scan, the records
   uint32_t* pk_counts = nullptr;
   uint64_t* pk_base = nullptr;
-  uint64_t* pk_stage = nullptr;
-  uint64_t pk_stage_bytes = 0;
+  gg_dbuf<uint8_t> pk_stage;            // (sized in bytes; holds uint64_t records)
   // gg_coherent_run_many with this context first: the live pairs and the poll
   // words, device and pinned host ([cap] ManyPair then [cap] ManyPoll each)
-  void* many_dev = nullptr;
-  void* many_host = nullptr;
-  uint32_t many_cap = 0;
+  gg_dbuf<uint8_t> many_dev;
+  gg_dbuf<uint8_t, gg_mem_pinned> many_host;
   uint32_t* bar_flag = nullptr;
   // live kernel timing (gg_set_timing): an event pair around every
   // kTimeSample-th launch of each kernel (mode 1; a pair around every launch,
@@ -303,9 +301,7 @@ static const char* kKernelNames[5] = {"coherent_step", "coherent_walk_x", "coher
 
 template <class F> static void timed_launch(gg_ctx* ctx, gg_coh_state* C, hipStream_t s, int kind, F&& fn)
 {
-  if (ctx->timing >= 2 && !C->kt_dev)
-    if (hipMalloc((void**)&C->kt_dev, sizeof(unsigned long long) * (size_t)C->S.kt_stride * kKtRing) == hipSuccess)
-      C->allocs.push_back((void*)C->kt_dev);
+  if (ctx->timing >= 2 && !C->kt_dev) C->mem.alloc(&C->kt_dev, (uint64_t)C->S.kt_stride * kKtRing);   // (failure: no in-kernel spans)
   if (ctx->timing >= 2 && C->kt_dev && kind < 3 && C->kt_kind.size() < kKtRing) {
     C->nlaunch[kind]++;
     cs_set(C->S.kt, C->kt_dev);
@@ -383,19 +379,10 @@ static hipError_t coh_pool_reset(gg_coh_state* C, hipStream_t s)
 static int clog2(uint64_t v) { int p = ilog2(v); return ((1ull << p) == v) ? p : p + 1; }
 static uint64_t lat_ps_host(uint64_t cycles, double f) { return (uint64_t)ceil(((double)1000 * cycles) / f); }
 
-template <class T> static gg_status dalloc(gg_coh_state* C, T** p, uint64_t n)
-{
-  void* v = nullptr;
-  hipError_t e = hipMalloc(&v, sizeof(T) * (n ? n : 1));
-  if (e != hipSuccess) return gg_hip_check(e, "hipMalloc(coherent state)");
-  *p = (T*)v;
-  C->allocs.push_back(v);
-  return GG_OK;
-}
 template <class D, class T> static gg_status dupload(gg_coh_state* C, D* p, const std::vector<T>& v)
 {
   T* d = nullptr;
-  if (gg_status st = dalloc(C, &d, v.size())) return st;
+  if (gg_status st = C->mem.alloc(&d, v.size())) return st;
   if (!v.empty()) GG_HIP(hipMemcpy(d, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice));
   cs_set(*p, d);
   return GG_OK;
@@ -404,7 +391,7 @@ template <class D, class T> static gg_status dupload(gg_coh_state* C, D* p, cons
 // an array of coh_alloc's list: allocated, and entered by name and size
 template <class T> static gg_status arr_alloc(gg_coh_state* C, const char* name, T** p, uint64_t n)
 {
-  if (gg_status st = dalloc(C, p, n)) return st;
+  if (gg_status st = C->mem.alloc(p, n)) return st;
   C->arrs.push_back(gg_coh_state::Arr{name, (void*)*p, sizeof(T) * n});
   return GG_OK;
 }
@@ -426,11 +413,7 @@ void gg_coh_free(gg_ctx* ctx)
 {
   gg_coh_state* C = ctx->coh;
   if (!C) return;
-  if (C->pk_stage) hipFree(C->pk_stage);
   for (hipEvent_t e : C->tev) hipEventDestroy(e);
-  for (void* p : C->allocs) hipFree(p);
-  if (C->many_dev) hipFree(C->many_dev);
-  if (C->many_host) hipHostFree(C->many_host);
   delete C;
   ctx->coh = nullptr;
 }
@@ -682,16 +665,16 @@ static gg_status coh_alloc(gg_ctx* ctx)
                     "(tools/build_variant.sh diag -DGG_COH_DIAG=1; GG_LIB=variants/diag/libgraphite_gpu.so); ignored\n");
   if (diag && getenv("GG_COH_TRACE") && atoi(getenv("GG_COH_TRACE")) > 0) {
     S.tr_n = (uint32_t)atoi(getenv("GG_COH_TRACE"));
-    if ((st = dalloc(C, &S.trs, (size_t)S.tr_n * P.L * kTrStep))) return st;
-    if ((st = dalloc(C, &S.trw, (size_t)S.tr_n * 2 * S.tr_wb * 8))) return st;
+    if ((st = C->mem.alloc(&S.trs, (size_t)S.tr_n * P.L * kTrStep))) return st;
+    if ((st = C->mem.alloc(&S.trw, (size_t)S.tr_n * 2 * S.tr_wb * 8))) return st;
   }
   S.tre = nullptr; S.tre_n = 0;
   if (diag && getenv("GG_COH_TRACE_EV") && atoi(getenv("GG_COH_TRACE_EV")) > 0) {
     S.tre_n = (uint32_t)atoi(getenv("GG_COH_TRACE_EV"));
-    if ((st = dalloc(C, &S.tre, (size_t)S.tre_n * 2 * S.tr_wb * (kTrEvMax * 4 + 4)))) return st;
+    if ((st = C->mem.alloc(&S.tre, (size_t)S.tre_n * 2 * S.tr_wb * (kTrEvMax * 4 + 4)))) return st;
   }
   if (diag && getenv("GG_COH_PROFILE") && atoi(getenv("GG_COH_PROFILE"))) {
-    if ((st = dalloc(C, &S.prof, 1024 + 8 * 65536))) return st;
+    if ((st = C->mem.alloc(&S.prof, 1024 + 8 * 65536))) return st;
     GG_HIP(hipMemset(S.prof, 0, sizeof(unsigned long long) * (1024 + 8 * 65536)));
   }
   if (st) return st;
@@ -699,8 +682,8 @@ static gg_status coh_alloc(gg_ctx* ctx)
   // run alone (the packed arrays are not touched: 2 GB at 1024 tiles)
   for (const gg_coh_state::Arr& a : C->arrs)
     if (snap_policy(a.name) == SN_DENSE && a.bytes) GG_HIP(hipMemset(a.p, 0, a.bytes));
-  if ((st = dalloc(C, &C->pk_counts, L))) return st;
-  if ((st = dalloc(C, &C->pk_base, L + 1))) return st;
+  if ((st = C->mem.alloc(&C->pk_counts, L))) return st;
+  if ((st = C->mem.alloc(&C->pk_base, L + 1))) return st;
   S.quiet = S.ring + 4; S.imp = S.ring + 5; S.live = S.ring + 7;
   if ((st = dupload(C, &S.gtile, gtile))) return st;
   if ((st = dupload(C, &S.ltile, ltile))) return st;
@@ -714,11 +697,11 @@ static gg_status coh_alloc(gg_ctx* ctx)
       ti[l] = make_uint4(gtile[l], tseg[(size_t)gtile[l] * 2], tseg[(size_t)gtile[l] * 2 + 1], 0u);
     if ((st = dupload(C, &S.tinfo, ti))) return st;
   }
-  if ((st = dalloc(C, &C->status_dev, 4))) return st;
-  if ((st = dalloc(C, &C->Pd, 1))) return st;
-  if ((st = dalloc(C, &C->Sd, 1))) return st;
-  if ((st = dalloc(C, &C->ecount_dev, 2 * (uint64_t)P.K + 2))) return st;
-  if ((st = dalloc(C, &C->offs_dev, (uint64_t)P.T + 1))) return st;
+  if ((st = C->mem.alloc(&C->status_dev, 4))) return st;
+  if ((st = C->mem.alloc(&C->Pd, 1))) return st;
+  if ((st = C->mem.alloc(&C->Sd, 1))) return st;
+  if ((st = C->mem.alloc(&C->ecount_dev, 2 * (uint64_t)P.K + 2))) return st;
+  if ((st = C->mem.alloc(&C->offs_dev, (uint64_t)P.T + 1))) return st;
   cs_set(S.ctr, gg_noc_ctr(ctx));
   {
     gg::HQueue* q; gg::HNode* nd;
@@ -811,10 +794,7 @@ gg_status gg_coherent_begin(gg_ctx* ctx, const gg_trace* tr, uint64_t* access_ou
   GG_HIP(hipGetLastError());
   uint32_t hb = 0;
   if (tr->num_records) {
-    if (!C->bar_flag) {
-      GG_HIP(hipMalloc((void**)&C->bar_flag, sizeof(uint32_t)));
-      C->allocs.push_back(C->bar_flag);
-    }
+    if (!C->bar_flag) if (gg_status st = C->mem.alloc(&C->bar_flag, 1)) return st;
     GG_HIP(hipMemsetAsync(C->bar_flag, 0, sizeof(uint32_t), s));
     const uint64_t nb = std::min<uint64_t>(4096, (tr->num_records + 255) / 256);
     hipLaunchKernelGGL(k_has_barrier, dim3((uint32_t)nb), dim3(256), 0, s, tr->meta_dev, tr->num_records, C->bar_flag);
@@ -1303,19 +1283,12 @@ gg_status gg_coherent_run_many(gg_ctx* const* ctxs, uint32_t n, const gg_trace* 
   gg_coh_state* C0 = c0->coh;
   hipSetDevice(c0->device);
   hipStream_t s = (hipStream_t)stream;
-  if (C0->many_cap < n) {
-    if (C0->many_dev) hipFree(C0->many_dev);
-    if (C0->many_host) hipHostFree(C0->many_host);
-    C0->many_dev = C0->many_host = nullptr; C0->many_cap = 0;
-    const size_t bytes = (size_t)n * (sizeof(ManyPair) + sizeof(ManyPoll));
-    GG_HIP(hipMalloc(&C0->many_dev, bytes));
-    GG_HIP(hipHostMalloc(&C0->many_host, bytes, hipHostMallocDefault));
-    C0->many_cap = n;
-  }
-  ManyPair* pairs_d = (ManyPair*)C0->many_dev;
-  ManyPoll* poll_d = (ManyPoll*)(pairs_d + C0->many_cap);
-  ManyPair* pairs_h = (ManyPair*)C0->many_host;
-  ManyPoll* poll_h = (ManyPoll*)(pairs_h + C0->many_cap);
+  const uint64_t many_bytes = (uint64_t)n * (sizeof(ManyPair) + sizeof(ManyPoll));
+  if (gg_status st = gg_reserve_all(many_bytes, many_bytes, C0->many_dev, C0->many_host)) return st;
+  ManyPair* pairs_d = reinterpret_cast<ManyPair*>(C0->many_dev.get());
+  ManyPoll* poll_d = (ManyPoll*)(pairs_d + n);
+  ManyPair* pairs_h = reinterpret_cast<ManyPair*>(C0->many_host.get());
+  ManyPoll* poll_h = (ManyPoll*)(pairs_h + n);
 
   std::vector<gg_status> stv(n, GG_OK);
   std::vector<uint64_t> done(n, 0);
@@ -1500,15 +1473,6 @@ const gg_coh_state::Arr* find_arr(const gg_coh_state* C, const char* name)
 {
   for (const gg_coh_state::Arr& a : C->arrs) if (!std::strcmp(a.name, name)) return &a;
   return nullptr;
-}
-gg_status stage_grow(gg_coh_state* C, uint64_t bytes)
-{
-  if (bytes <= C->pk_stage_bytes) return GG_OK;
-  if (C->pk_stage) hipFree(C->pk_stage);
-  C->pk_stage = nullptr; C->pk_stage_bytes = 0;
-  GG_HIP(hipMalloc((void**)&C->pk_stage, bytes));
-  C->pk_stage_bytes = bytes;
-  return GG_OK;
 }
 gg_status snap_valid(gg_ctx* ctx, const char* what)
 {
@@ -1743,9 +1707,9 @@ static gg_status coh_snapshot(gg_ctx* ctx, uint8_t* host_buf, uint64_t cap, uint
   for (size_t i = 0; i < pk.size(); ++i) {
     const ggsnap::Section& sec = lay.sec[first_pk + i];
     if (!sec.bytes) continue;
-    if (gg_status e = stage_grow(C, sec.bytes)) return e;
+    if (gg_status e = C->pk_stage.reserve(sec.bytes)) return e;
     GG_HIP(hipMemcpyAsync(C->pk_base, base[i].data(), sizeof(uint64_t) * (P.L + 1), hipMemcpyHostToDevice, s));
-    GG_HIP(snap_pack(pk[i].src, C->pk_base, sec.records, C->pk_stage, s));
+    GG_HIP(snap_pack(pk[i].src, C->pk_base, sec.records, reinterpret_cast<uint64_t*>(C->pk_stage.get()), s));
     GG_HIP(hipMemcpyAsync(at(first_pk + i), C->pk_stage, sec.bytes, hipMemcpyDeviceToHost, s));
     GG_HIP(hipStreamSynchronize(s));
   }
@@ -1864,9 +1828,9 @@ gg_status gg_coherent_restore(gg_ctx* ctx, const gg_trace* tr, uint64_t* access_
   for (const SnapPacked& p : pk) {
     x = v.find(p.name);
     if (!x->bytes) continue;
-    if (gg_status st = stage_grow(C, x->bytes)) return st;
+    if (gg_status st = C->pk_stage.reserve(x->bytes)) return st;
     GG_HIP(hipMemcpyAsync(C->pk_stage, v.data(*x), x->bytes, hipMemcpyHostToDevice, s));
-    GG_HIP(snap_unpack(p.src, C->pk_stage, x->records, s));
+    GG_HIP(snap_unpack(p.src, reinterpret_cast<const uint64_t*>(C->pk_stage.get()), x->records, s));
     GG_HIP(hipStreamSynchronize(s));
   }
   GG_HIP(hipStreamSynchronize(s));

@@ -419,17 +419,6 @@ uint64_t cycle_ps(double f_ghz) { return (uint64_t)ceil(((double)1000 * 1) / f_g
 
 }  // namespace
 
-void gg_core_free(gg_ctx* ctx)
-{
-  if (ctx->core_dev) hipFree(ctx->core_dev);
-  if (ctx->core_tasks) hipFree(ctx->core_tasks);
-  ctx->core_dev = nullptr; ctx->core_tasks = nullptr; ctx->core_task_cap = 0; ctx->core_valid = false;
-  if (ctx->io_stats) hipFree(ctx->io_stats);
-  if (ctx->io_offs) hipFree(ctx->io_offs);
-  if (ctx->io_err) hipFree(ctx->io_err);
-  ctx->io_stats = nullptr; ctx->io_offs = nullptr; ctx->io_err = nullptr; ctx->io_valid = false;
-}
-
 extern "C" {
 
 gg_status gg_core_model_run(gg_ctx* ctx, const gg_trace* tr, const uint64_t* access_out_dev, void* stream)
@@ -452,20 +441,15 @@ gg_status gg_core_model_run(gg_ctx* ctx, const gg_trace* tr, const uint64_t* acc
     for (uint64_t b = off[t]; b < off[t + 1]; b += kTaskRecords)
       tasks.push_back(CoreTask{b, std::min(off[t + 1], b + kTaskRecords), off[t], t, 0});
   if (tasks.size() > 0xFFFFFFFFull / 2) return gg_fail(GG_ERR_RANGE, "gg_core_model_run: trace too long");
-  if (!ctx->core_dev) GG_HIP(hipMalloc((void**)&ctx->core_dev, sizeof(uint64_t) * T * GG_NUM_CORE_STATS));
-  if (tasks.size() > ctx->core_task_cap) {
-    if (ctx->core_tasks) hipFree(ctx->core_tasks);
-    ctx->core_tasks = nullptr; ctx->core_task_cap = 0;
-    GG_HIP(hipMalloc(&ctx->core_tasks, sizeof(CoreTask) * tasks.size()));
-    ctx->core_task_cap = tasks.size();
-  }
+  if (gg_status st = ctx->core_dev.reserve((uint64_t)T * GG_NUM_CORE_STATS)) return st;
+  if (gg_status st = ctx->core_tasks.reserve(sizeof(CoreTask) * tasks.size())) return st;
   GG_HIP(hipMemsetAsync(ctx->core_dev, 0, sizeof(uint64_t) * T * GG_NUM_CORE_STATS, s));
   if (!tasks.empty()) {
     GG_HIP(hipMemcpyAsync(ctx->core_tasks, tasks.data(), sizeof(CoreTask) * tasks.size(), hipMemcpyHostToDevice, s));
     const uint32_t nt = (uint32_t)tasks.size();
     gg_timer_begin(ctx, "core_model", s);
     hipLaunchKernelGGL(k_core_model, dim3((nt + kCoreWaves - 1) / kCoreWaves), dim3(64 * kCoreWaves), 0, s,
-                       tr->meta_dev, access_out_dev, (const CoreTask*)ctx->core_tasks, nt,
+                       tr->meta_dev, access_out_dev, reinterpret_cast<const CoreTask*>(ctx->core_tasks.get()), nt,
                        cycle_ps(ctx->cfg.frequency_ghz), ctx->core_dev);
     GG_HIP(hipGetLastError());
     gg_timer_end(ctx, "core_model", s);
@@ -510,11 +494,9 @@ gg_status gg_iocoom_run(gg_ctx* ctx, const gg_iocoom_params* params, const gg_in
   hipSetDevice(ctx->device);
   hipStream_t s = (hipStream_t)stream;
   ctx->last_stream = s;
-  if (!ctx->io_stats) {
-    GG_HIP(hipMalloc((void**)&ctx->io_stats, sizeof(uint64_t) * T * GG_NUM_IOCOOM_STATS));
-    GG_HIP(hipMalloc((void**)&ctx->io_offs, sizeof(uint64_t) * 2 * (T + 1)));
-    GG_HIP(hipMalloc((void**)&ctx->io_err, sizeof(uint32_t)));
-  }
+  if (gg_status st = ctx->io_stats.reserve((uint64_t)T * GG_NUM_IOCOOM_STATS)) return st;
+  if (gg_status st = ctx->io_offs.reserve(2 * ((uint64_t)T + 1))) return st;
+  if (gg_status st = ctx->io_err.reserve(1)) return st;
   std::vector<uint64_t> offs(2 * (size_t)(T + 1));
   std::copy(ins_tile_offsets, ins_tile_offsets + T + 1, offs.begin());
   std::copy(acc_tile_offsets, acc_tile_offsets + T + 1, offs.begin() + T + 1);

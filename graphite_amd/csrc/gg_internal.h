@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/graphite_gpu.h"
+#include "gg_devmem.h"
 
 #define GG_WAVE 64
 #define GG_NUM_XCD 8          // MI355X: 8 XCDs, workgroups dealt round-robin by blockIdx
@@ -89,20 +90,19 @@ struct gg_ctx {
   int device = 0;
   int num_cus = 256;
   hipStream_t last_stream = nullptr;
+  gg_arena mem;                  // owns what lives as long as the context: cs, err_dev, unit_*, total_dev, tile_off_dev
+                                 // (raw pointers below; gg_devmem.h)
   gg_cache_state cs{};
   uint32_t* err_dev = nullptr;
   // batch scratch (grown on demand)
-  uint64_t* sh_key = nullptr;    // sharded records (slot order): line address | write bit
-  uint32_t* sh_res = nullptr;    // replay results in slot order
-  uint64_t* sh_ev = nullptr;     // evicted L2 line addresses in slot order (only when requested)
-  uint64_t  sh_cap = 0, sh_res_cap = 0, sh_ev_cap = 0;
-  uint32_t* rec_slot = nullptr;  // [records] slot of each program-order record (written by the scatter)
-  uint64_t  rec_cap = 0;
-  uint32_t* chunk_cnt = nullptr; // [chunks][u1]
-  uint32_t* chunk_tile = nullptr;
-  uint64_t* chunk_start = nullptr;
-  uint32_t* chunk_len = nullptr;
-  uint64_t  chunk_cap = 0;
+  gg_dbuf<uint64_t> sh_key;      // sharded records (slot order): line address | write bit
+  gg_dbuf<uint32_t> sh_res;      // replay results in slot order
+  gg_dbuf<uint64_t> sh_ev;       // evicted L2 line addresses in slot order (only when requested)
+  gg_dbuf<uint32_t> rec_slot;    // [records] slot of each program-order record (written by the scatter)
+  gg_dbuf<uint32_t> chunk_cnt;   // [chunks][u1]
+  gg_dbuf<uint32_t> chunk_tile;  // the chunk tables share one capacity (in chunks)
+  gg_dbuf<uint64_t> chunk_start;
+  gg_dbuf<uint32_t> chunk_len;
   uint32_t* unit_len = nullptr;  // [units]
   uint64_t* unit_base = nullptr; // [units] slot of the unit's record 0 (records contiguous, padded to 8)
   uint64_t* total_dev = nullptr; // slots of the sharded layout
@@ -120,23 +120,24 @@ struct gg_ctx {
   // capacity per (tile, cache) in lines, and whether the private cache state
   // has been touched since gg_create / gg_reset (the opt-in needs it fresh)
   gg_mt_view mt{};
+  gg_dbuf<uint64_t> mt_tab;                // mt.tab / mt.cnt
+  gg_dbuf<unsigned long long> mt_cnt;
   uint64_t mt_lines = 0;
   bool cache_dirty = false;
   // timing
   int timing = 0;                // gg_set_timing: 0 off, 1 sampled coherent launches, 2 every launch
   std::vector<gg_timer> timers;
   // core timing (gg_core.hip): [tiles][GG_NUM_CORE_STATS] and its task list
-  uint64_t* core_dev = nullptr;
-  void* core_tasks = nullptr;
-  uint64_t core_task_cap = 0;
+  gg_dbuf<uint64_t> core_dev;
+  gg_dbuf<uint8_t> core_tasks;   // CoreTask records
   bool core_valid = false;
   // the iocoom core model (gg_core.hip): [tiles][GG_NUM_IOCOOM_STATS], the
   // two offset lists [2][tiles + 1] and the stream-check word
-  uint64_t* io_stats = nullptr;
-  uint64_t* io_offs = nullptr;
-  uint32_t* io_err = nullptr;
+  gg_dbuf<uint64_t> io_stats;
+  gg_dbuf<uint64_t> io_offs;
+  gg_dbuf<uint32_t> io_err;
   bool io_valid = false;
-  // multi-rank round buffers (gg_round.hip), freed by gg_destroy
+  // multi-rank round buffers (gg_round.hip), deleted by gg_destroy through round_free
   void* round = nullptr;
   void (*round_free)(void*) = nullptr;
   // statistics trace (gg_stats.hip), allocated by gg_stats_trace_configure
@@ -162,7 +163,6 @@ void gg_timer_end(gg_ctx* ctx, const char* name, hipStream_t s);
 
 // cache path (gg_cache.hip)
 gg_status gg_cache_state_alloc(gg_ctx* ctx);
-void      gg_cache_state_free(gg_ctx* ctx);
 gg_status gg_cache_state_reset(gg_ctx* ctx, hipStream_t s);
 gg_status gg_cache_run_batch(gg_ctx* ctx, const gg_trace* tr, uint32_t* result, uint64_t* evicted, hipStream_t s);
 gg_status gg_cache_quartet(gg_ctx* ctx, int op, uint32_t tile, int level, uint64_t addr,
@@ -178,8 +178,6 @@ gg_status gg_noc_run(gg_ctx* ctx, const gg_packets* pk, const gg_packet_out* out
 gg_status gg_noc_tree(gg_ctx* ctx, const gg_packets* pk, const gg_packet_out* out, const gg_packet_out* bout,
                       uint64_t nb, hipStream_t s);
 gg_status gg_noc_counters(gg_ctx* ctx, uint64_t* out);
-// core timing (gg_core.hip)
-void      gg_core_free(gg_ctx* ctx);
 // coherent path (gg_coherent.hip)
 void      gg_coh_free(gg_ctx* ctx);
 gg_status gg_htree_run(gg_ctx* ctx, uint64_t min_proc, const uint64_t* t, const uint64_t* p, uint64_t n, uint64_t* d);

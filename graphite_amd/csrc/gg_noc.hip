@@ -2002,19 +2002,19 @@ __global__ __launch_bounds__(kTgThreads) void k_tree_grid(NocDev D, TreeIO IO, T
 
 struct gg_noc_state {
   NocParams P;
+  gg_arena mem;                                   // owns q, nd, ctr, prof
   HQueue* q = nullptr; HNode* nd = nullptr; uint64_t nq = 0;
   uint64_t* ctr = nullptr;
-  // batch scratch
-  uint64_t cap = 0;
-  uint64_t *t = nullptr, *zl = nullptr, *ct = nullptr;
-  uint32_t *cur = nullptr, *keys = nullptr, *ids = nullptr;
-  Ev* heap = nullptr;
-  uint32_t* counts = nullptr; uint32_t* cursor = nullptr; uint64_t* off = nullptr; uint32_t nb_cap = 0;
-  TEv* theap = nullptr; uint32_t* bidx = nullptr; uint64_t tcap = 0, bcap = 0;   // broadcast-tree walk scratch
+  // batch scratch: the packet arrays share one capacity, the bucket arrays another
+  gg_dbuf<uint64_t> t, zl, ct;
+  gg_dbuf<uint32_t> cur, keys, ids;
+  gg_dbuf<Ev> heap;
+  gg_dbuf<uint32_t> counts, cursor; gg_dbuf<uint64_t> off;
+  gg_dbuf<TEv> theap; gg_dbuf<uint32_t> bidx;     // broadcast-tree walk scratch
   unsigned long long* prof = nullptr;             // GG_NOC_PROFILE=1: k_chain_sweep phase cycles (diagnostics)
-  SK* pscr = nullptr; uint64_t pscr_cap = 0;       // k_chain_pipe: per packet 3 x positions pool / incoming slots
-  uint8_t* tp = nullptr; uint64_t tp_bytes = 0;     // k_tree_pool: TpBufs
-  uint8_t* tg = nullptr; uint64_t tg_bytes = 0;     // k_tree_setup / k_tree_grid: TgBufs
+  gg_dbuf<SK> pscr;                               // k_chain_pipe: per packet 3 x positions pool / incoming slots
+  gg_dbuf<uint8_t> tp;                            // k_tree_pool: TpBufs
+  gg_dbuf<uint8_t> tg;                            // k_tree_setup / k_tree_grid: TgBufs
 };
 
 gg_status gg_noc_alloc(gg_ctx* ctx)
@@ -2040,7 +2040,7 @@ gg_status gg_noc_alloc(gg_ctx* ctx)
   if (gg_status e = gg_check_queue_model(c.queue_model_type, P.qaux, P.max_size)) return e;
   if (getenv("GG_NOC_PROFILE") && atoi(getenv("GG_NOC_PROFILE"))) {
     if (!GG_NOC_DIAG) fprintf(stderr, "[gg_noc] GG_NOC_PROFILE needs a diagnostics build (-DGG_NOC_DIAG=1)\n");
-    GG_HIP(hipMalloc((void**)&S->prof, 32 * sizeof(unsigned long long)));
+    if (gg_status st = S->mem.alloc(&S->prof, 32)) return st;
     GG_HIP(hipMemset(S->prof, 0, 32 * sizeof(unsigned long long)));
     GG_HIP(hipMemset(S->prof + 25, 0xFF, sizeof(unsigned long long)));
   }
@@ -2053,25 +2053,20 @@ gg_status gg_noc_alloc(gg_ctx* ctx)
   GG_HIP(hipFuncSetAttribute((const void*)k_tree_grid, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTpLds));
   GG_HIP(hipFuncSetAttribute((const void*)k_tree_walk<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)(kTreeLdsEv * sizeof(TEv))));
-  GG_HIP(hipMalloc((void**)&S->ctr, sizeof(uint64_t) * c.num_tiles * GG_NUM_NET_COUNTERS));
+  if (gg_status st = S->mem.alloc(&S->ctr, (uint64_t)c.num_tiles * GG_NUM_NET_COUNTERS)) return st;
   // one history tree per mesh output port (5) + the injection port, per tile; the
   // stand-alone gg_queue_delay_batch queue lives at index tiles*6
   S->nq = (uint64_t)c.num_tiles * 6 + 1;
-  GG_HIP(hipMalloc((void**)&S->q, sizeof(HQueue) * S->nq));
-  GG_HIP(hipMalloc((void**)&S->nd, sizeof(HNode) * S->nq * P.max_size));
+  if (gg_status st = S->mem.alloc(&S->q, S->nq)) return st;
+  if (gg_status st = S->mem.alloc(&S->nd, S->nq * P.max_size)) return st;
   if (c.net_model == GG_NET_ATAC) return gg_atac_alloc(ctx, nullptr);
   return GG_OK;
 }
 
 void gg_noc_free(gg_ctx* ctx)
 {
-  gg_noc_state* S = ctx->noc;
   gg_atac_free(ctx);
-  if (!S) return;
-  void* ps[] = {S->q, S->nd, S->ctr, S->t, S->zl, S->ct, S->cur, S->keys, S->ids, S->heap,
-                S->counts, S->cursor, S->off, S->theap, S->bidx, S->prof, S->pscr, S->tp, S->tg};
-  for (void* p : ps) if (p) hipFree(p);
-  delete S;
+  delete ctx->noc;
   ctx->noc = nullptr;
 }
 
@@ -2088,24 +2083,8 @@ gg_status gg_noc_reset(gg_ctx* ctx, hipStream_t s)
 
 static gg_status noc_grow(gg_noc_state* S, uint64_t n, uint32_t nb)
 {
-  if (n > S->cap) {
-    void* ps[] = {S->t, S->zl, S->ct, S->cur, S->keys, S->ids, S->heap};
-    for (void* p : ps) if (p) hipFree(p);
-    uint64_t c = n + n / 4 + 1024;
-    GG_HIP(hipMalloc((void**)&S->t, 8 * c)); GG_HIP(hipMalloc((void**)&S->zl, 8 * c));
-    GG_HIP(hipMalloc((void**)&S->ct, 8 * c)); GG_HIP(hipMalloc((void**)&S->cur, 4 * c));
-    GG_HIP(hipMalloc((void**)&S->keys, 4 * c)); GG_HIP(hipMalloc((void**)&S->ids, 4 * c));
-    GG_HIP(hipMalloc((void**)&S->heap, sizeof(Ev) * c));
-    S->cap = c;
-  }
-  if (nb > S->nb_cap) {
-    if (S->counts) { hipFree(S->counts); hipFree(S->cursor); hipFree(S->off); }
-    GG_HIP(hipMalloc((void**)&S->counts, 4 * (nb + 1)));
-    GG_HIP(hipMalloc((void**)&S->cursor, 4 * (nb + 1)));
-    GG_HIP(hipMalloc((void**)&S->off, 8 * (nb + 1)));
-    S->nb_cap = nb;
-  }
-  return GG_OK;
+  if (gg_status st = gg_reserve_all(n, n + n / 4 + 1024, S->t, S->zl, S->ct, S->cur, S->keys, S->ids, S->heap)) return st;
+  return gg_reserve_all((uint64_t)nb + 1, (uint64_t)nb + 1, S->counts, S->cursor, S->off);
 }
 
 gg_status gg_noc_run(gg_ctx* ctx, const gg_packets* pk, const gg_packet_out* out, hipStream_t s)
@@ -2190,23 +2169,11 @@ gg_status gg_noc_tree(gg_ctx* ctx, const gg_packets* pk, const gg_packet_out* ou
   const bool pool = win && !gridf && tp_ecap >= 64;
   const bool lds = !gridf && !pool && hcap <= kTreeLdsEv;
   const uint64_t need = gridf || pool || lds ? 0 : hcap;
-  if (need > S->tcap) {
-    if (S->theap) hipFree(S->theap);
-    GG_HIP(hipMalloc((void**)&S->theap, sizeof(TEv) * need));
-    S->tcap = need;
-  }
-  if (n > S->bcap) {
-    if (S->bidx) hipFree(S->bidx);
-    GG_HIP(hipMalloc((void**)&S->bidx, 4 * n));
-    S->bcap = n;
-  }
+  if (gg_status st = S->theap.reserve(need)) return st;
+  if (gg_status st = S->bidx.reserve(n)) return st;
   TgBufs GB{};
   if (gridf) {
-    if (tg_need > S->tg_bytes) {
-      if (S->tg) hipFree(S->tg);
-      GG_HIP(hipMalloc((void**)&S->tg, tg_need));
-      S->tg_bytes = tg_need;
-    }
+    if (gg_status st = S->tg.reserve(tg_need)) return st;
     uint8_t* b = S->tg;
     auto take = [&](uint64_t bytes) { uint8_t* r = b; b += (bytes + 15) & ~15ull; return r; };
     GB.pk = reinterpret_cast<TEv*>(take(n * sizeof(TEv)));
@@ -2226,12 +2193,8 @@ gg_status gg_noc_tree(gg_ctx* ctx, const gg_packets* pk, const gg_packet_out* ou
   TpBufs TB{};
   if (pool) {
     const uint64_t need_b = 2 * n * sizeof(TEv) + 2 * hcap * sizeof(TEv) + hcap * sizeof(TGe);
-    if (need_b > S->tp_bytes) {
-      if (S->tp) hipFree(S->tp);
-      GG_HIP(hipMalloc((void**)&S->tp, need_b));
-      S->tp_bytes = need_b;
-    }
-    TEv* e = reinterpret_cast<TEv*>(S->tp);
+    if (gg_status st = S->tp.reserve(need_b)) return st;
+    TEv* e = reinterpret_cast<TEv*>(S->tp.get());
     TB.run = e; TB.heap = e + n; TB.hp[0] = e + 2 * n; TB.hp[1] = e + 2 * n + hcap;
     TB.gh = reinterpret_cast<TGe*>(e + 2 * n + 2 * hcap);
   }
@@ -2347,12 +2310,7 @@ static gg_status noc_hbh_stages(gg_ctx* ctx, const uint32_t* src, const uint32_t
                            S->heap, PS);
     } else if (staged && std::max(P.w, P.h) <= kPipePos) {
       const uint64_t stride = 3ull * std::max(P.w, P.h);
-      if (S->pscr_cap < cap * stride) {
-        if (S->pscr) hipFree(S->pscr);
-        S->pscr = nullptr; S->pscr_cap = 0;
-        GG_HIP(hipMalloc((void**)&S->pscr, sizeof(SK) * cap * stride));
-        S->pscr_cap = cap * stride;
-      }
+      if (gg_status st = S->pscr.reserve(cap * stride)) return st;
       hipLaunchKernelGGL(k_chain_pipe, dim3(nb), dim3(64 * kPipeWaves), kStageLdsMax, s, D, stage - 1, dst, len, S->off,
                          S->ids, S->heap, PS, S->pscr, stride, P.net_model == GG_NET_ATAC ? kPipePkEnet : kPipePk, S->prof);
     } else if (staged) {
@@ -2403,8 +2361,9 @@ gg_status gg_htree_run(gg_ctx* ctx, uint64_t min_proc, const uint64_t* t, const 
   const uint64_t qi = (uint64_t)S->P.tiles * 6;   // the stand-alone queue
   hipLaunchKernelGGL(k_htree_reset, dim3(1), dim3(1), 0, s, S->q + qi, S->nd + qi * S->P.max_size,
                      1ull, S->P.max_size, S->P.qtype, S->P.qaux);
-  uint64_t* buf = nullptr;
-  GG_HIP(hipMalloc((void**)&buf, 24 * (n ? n : 1)));
+  gg_dbuf<uint64_t> dbuf;
+  if (gg_status st = dbuf.reserve(3 * (n ? n : 1))) return st;
+  uint64_t* const buf = dbuf.get();
   GG_HIP(hipMemcpyAsync(buf, t, 8 * n, hipMemcpyHostToDevice, s));
   GG_HIP(hipMemcpyAsync(buf + n, p, 8 * n, hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_htree_seq, dim3(1), dim3(64), 0, s, S->q + qi, S->nd + qi * S->P.max_size,
@@ -2412,7 +2371,6 @@ gg_status gg_htree_run(gg_ctx* ctx, uint64_t min_proc, const uint64_t* t, const 
   GG_HIP(hipGetLastError());
   GG_HIP(hipMemcpyAsync(d, buf + 2 * n, 8 * n, hipMemcpyDeviceToHost, s));
   GG_HIP(hipStreamSynchronize(s));
-  hipFree(buf);
   return GG_OK;
 }
 

@@ -565,28 +565,22 @@ struct gg_atac_state {
   gg_atac_params A{};
   uint32_t C = 0;
   uint64_t nq = 0;
+  gg_arena mem;            // owns the topology tables, q, nd and actr
   uint32_t *cluster_of = nullptr, *ap_of = nullptr, *hub_of = nullptr, *star_of = nullptr, *members = nullptr;
   HQueue* q = nullptr; HNode* nd = nullptr;
   uint64_t* actr = nullptr;
-  // batch scratch
-  uint64_t pcap = 0, rcap = 0; uint32_t nb_cap = 0;
-  uint8_t* route = nullptr;
-  uint32_t *dinj = nullptr, *dxy = nullptr, *dself = nullptr, *bidx = nullptr, *bpkt = nullptr, *nbc = nullptr;
-  uint64_t *rt = nullptr, *rzl = nullptr, *rct = nullptr, *dhub = nullptr, *dstar = nullptr;
-  uint32_t *keys = nullptr, *ids = nullptr;
-  SK* scr = nullptr;
-  uint32_t *counts = nullptr, *cursor = nullptr; uint64_t* off = nullptr;
+  // batch scratch: the per-packet arrays share one capacity, the per-record arrays another
+  gg_dbuf<uint8_t> route;
+  gg_dbuf<uint32_t> dinj, dxy, dself, bidx, bpkt, nbc;
+  gg_dbuf<uint64_t> rt, rzl, rct, dhub, dstar;
+  gg_dbuf<uint32_t> keys, ids;
+  gg_dbuf<SK> scr;
+  gg_dbuf<uint32_t> counts, cursor; gg_dbuf<uint64_t> off;
 };
 
 void gg_atac_free(gg_ctx* ctx)
 {
-  gg_atac_state* S = ctx->atac;
-  if (!S) return;
-  void* ps[] = {S->cluster_of, S->ap_of, S->hub_of, S->star_of, S->members, S->q, S->nd, S->actr, S->route, S->dinj,
-                S->dxy, S->dself, S->bidx, S->bpkt, S->nbc, S->rt, S->rzl, S->rct, S->dhub, S->dstar, S->keys, S->ids, S->scr,
-                S->counts, S->cursor, S->off};
-  for (void* p : ps) if (p) hipFree(p);
-  delete S;
+  delete ctx->atac;
   ctx->atac = nullptr;
 }
 
@@ -606,7 +600,7 @@ gg_status gg_atac_alloc(gg_ctx* ctx, const gg_atac_params* p)
   std::vector<uint32_t> cl(T), ap(T), hub(t.C), star(T), mem(T);
   atac_topology(T, A, t, cl.data(), ap.data(), hub.data(), star.data(), mem.data());
   auto up = [&](uint32_t** d, const std::vector<uint32_t>& h) -> gg_status {
-    GG_HIP(hipMalloc((void**)d, 4 * h.size()));
+    if (gg_status st = S->mem.alloc(d, h.size())) return st;
     GG_HIP(hipMemcpy(*d, h.data(), 4 * h.size(), hipMemcpyHostToDevice));
     return GG_OK;
   };
@@ -617,9 +611,9 @@ gg_status gg_atac_alloc(gg_ctx* ctx, const gg_atac_params* p)
   if (gg_status st = up(&S->members, mem)) return st;
   const uint64_t G = (uint64_t)t.C * A.num_receive_nets;
   S->nq = (uint64_t)T + t.C + G * (1 + (A.receive_net_type == GG_ATAC_STAR ? A.cluster_size : 0));
-  GG_HIP(hipMalloc((void**)&S->q, sizeof(HQueue) * S->nq));
-  GG_HIP(hipMalloc((void**)&S->nd, sizeof(HNode) * S->nq * P.max_size));
-  GG_HIP(hipMalloc((void**)&S->actr, sizeof(uint64_t) * T * GG_NUM_ATAC_COUNTERS));
+  if (gg_status st = S->mem.alloc(&S->q, S->nq)) return st;
+  if (gg_status st = S->mem.alloc(&S->nd, S->nq * P.max_size)) return st;
+  if (gg_status st = S->mem.alloc(&S->actr, (uint64_t)T * GG_NUM_ATAC_COUNTERS)) return st;
   GG_HIP(hipFuncSetAttribute((const void*)k_atac_port<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kALds));
   GG_HIP(hipFuncSetAttribute((const void*)k_atac_port<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kALds));
   GG_HIP(hipFuncSetAttribute((const void*)k_atac_receive, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRLds));
@@ -641,40 +635,13 @@ gg_status gg_atac_reset(gg_ctx* ctx, hipStream_t s)
 
 static gg_status atac_grow(gg_atac_state* S, uint64_t n, uint64_t nrec, uint64_t nbc, uint32_t nbuckets)
 {
-  if (n > S->pcap) {
-    void* ps[] = {S->route, S->dinj, S->dxy, S->dself, S->bidx};
-    for (void* p : ps) if (p) hipFree(p);
-    S->route = nullptr; S->dinj = S->dxy = S->dself = S->bidx = nullptr; S->pcap = 0;
-    const uint64_t c = n + n / 4 + 1024;
-    GG_HIP(hipMalloc((void**)&S->route, c)); GG_HIP(hipMalloc((void**)&S->dinj, 4 * c));
-    GG_HIP(hipMalloc((void**)&S->dxy, 4 * c)); GG_HIP(hipMalloc((void**)&S->dself, 4 * c));
-    GG_HIP(hipMalloc((void**)&S->bidx, 4 * c));
-    S->pcap = c;
-  }
-  if (nrec > S->rcap) {
-    void* ps[] = {S->rt, S->rzl, S->rct, S->dhub, S->dstar, S->keys, S->ids, S->scr};
-    for (void* p : ps) if (p) hipFree(p);
-    S->rt = S->rzl = S->rct = S->dhub = S->dstar = nullptr; S->keys = S->ids = nullptr; S->scr = nullptr; S->rcap = 0;
-    const uint64_t c = nrec + nrec / 4 + 1024;
-    GG_HIP(hipMalloc((void**)&S->rt, 8 * c)); GG_HIP(hipMalloc((void**)&S->rzl, 8 * c)); GG_HIP(hipMalloc((void**)&S->rct, 8 * c));
-    GG_HIP(hipMalloc((void**)&S->dhub, 8 * c)); GG_HIP(hipMalloc((void**)&S->dstar, 8 * c));
-    GG_HIP(hipMalloc((void**)&S->keys, 4 * c)); GG_HIP(hipMalloc((void**)&S->ids, 4 * c));
-    GG_HIP(hipMalloc((void**)&S->scr, sizeof(SK) * c));
-    S->rcap = c;
-  }
-  if (nbc + 1 > S->nb_cap || !S->bpkt) {
-    if (S->bpkt) hipFree(S->bpkt);
-    S->bpkt = nullptr;
-    GG_HIP(hipMalloc((void**)&S->bpkt, 4 * (nbc + 1024)));
-    S->nb_cap = (uint32_t)std::min<uint64_t>(nbc + 1024, 0xFFFFFFFFull);
-  }
-  if (!S->nbc) GG_HIP(hipMalloc((void**)&S->nbc, 4));
-  if (!S->counts) {
-    GG_HIP(hipMalloc((void**)&S->counts, 4 * ((uint64_t)nbuckets + 1)));
-    GG_HIP(hipMalloc((void**)&S->cursor, 4 * ((uint64_t)nbuckets + 1)));
-    GG_HIP(hipMalloc((void**)&S->off, 8 * ((uint64_t)nbuckets + 1)));
-  }
-  return GG_OK;
+  if (gg_status st = gg_reserve_all(n, n + n / 4 + 1024, S->route, S->dinj, S->dxy, S->dself, S->bidx)) return st;
+  if (gg_status st = gg_reserve_all(nrec, nrec + nrec / 4 + 1024, S->rt, S->rzl, S->rct, S->dhub, S->dstar, S->keys, S->ids,
+                                    S->scr))
+    return st;
+  if (gg_status st = S->bpkt.reserve(nbc + 1, nbc + 1024)) return st;
+  if (gg_status st = S->nbc.reserve(1)) return st;
+  return gg_reserve_all((uint64_t)nbuckets + 1, (uint64_t)nbuckets + 1, S->counts, S->cursor, S->off);   // one size per state
 }
 
 gg_status gg_atac_run(gg_ctx* ctx, const gg_packets* pk, const gg_packet_out* out, const gg_packet_out* bout, uint64_t nb,
@@ -737,7 +704,7 @@ gg_status gg_atac_run(gg_ctx* ctx, const gg_packets* pk, const gg_packet_out* ou
   if (star && P.qm) GG_HIP(hipMemsetAsync(S->dstar, 0, 8 * nrec, s));   // a broadcast's star delay: the max over the ports
   const uint32_t waves = std::min<uint32_t>(kRMaxWaves, star && P.qm ? 1 + S->A.cluster_size : 4u);
   hipLaunchKernelGGL(k_atac_receive, dim3(G), dim3(64 * waves), kRLds, s, D, K, S->off, S->ids, S->scr, S->dhub,
-                     reinterpret_cast<unsigned long long*>(S->dstar));
+                     reinterpret_cast<unsigned long long*>(S->dstar.get()));
   gg_timer_end(ctx, "noc_atac_receive", s);
   hipLaunchKernelGGL(k_atac_out, dim3(pblocks), dim3(256), 0, s, K);
   GG_HIP(hipGetLastError());

@@ -52,9 +52,9 @@ constexpr uint64_t kSlotDefault = 1024;   // records per peer and quantum sent i
 static_assert(GG_ROUND_WORDS == kRoundWords, "gg_internal.h kRoundWords");
 
 struct RoundBufs {
-  gg_cmsg* send = nullptr; gg_cmsg* recv = nullptr;   // [world][1 + region] each
-  uint64_t* dv = nullptr;                             // [1 + world][kRoundWords] own, gathered; [2 * world] slot counts
-  uint64_t* host = nullptr;                           // pinned copy of the gathered words and counts
+  gg_dbuf<gg_cmsg> send, recv;                        // [world][1 + region] each
+  gg_dbuf<uint64_t> dv;                               // [1 + world][kRoundWords] own, gathered; [2 * world] slot counts
+  gg_dbuf<uint64_t, gg_mem_pinned> host;              // pinned copy of the gathered words and counts
   uint64_t region = 0; int world = 0;
   uint32_t steps_hist[4] = {8, 8, 8, 8};              // steps of the last quanta (the batch predictor)
   uint32_t hist_i = 0;
@@ -80,25 +80,23 @@ struct RoundBufs {
 
 void bufs_free(void* p)
 {
-  RoundBufs* b = static_cast<RoundBufs*>(p);
-  hipFree(b->send); hipFree(b->recv); hipFree(b->dv); hipHostFree(b->host);
-  delete b;
+  delete static_cast<RoundBufs*>(p);
 }
 
 gg_status bufs_for(gg_ctx* ctx, RoundBufs*& B, int world, uint32_t rank, uint64_t region)
 {
   B = static_cast<RoundBufs*>(gg_round_state(ctx));
-  if (B && B->world == world && B->region >= region) return GG_OK;
+  if (B && B->world == world && B->region >= region && B->host) return GG_OK;   // (host: the last one allocated)
   if (B) bufs_free(B);
   gg_round_state_set(ctx, nullptr, nullptr);
   B = new RoundBufs();
   B->region = region; B->world = world; B->rank = rank;
   gg_round_state_set(ctx, B, bufs_free);
   const size_t slots = (size_t)world * (region + 1);
-  GG_HIP(hipMalloc((void**)&B->send, sizeof(gg_cmsg) * slots));
-  GG_HIP(hipMalloc((void**)&B->recv, sizeof(gg_cmsg) * slots));
-  GG_HIP(hipMalloc((void**)&B->dv, sizeof(uint64_t) * B->dv_words()));
-  GG_HIP(hipHostMalloc((void**)&B->host, sizeof(uint64_t) * B->dv_words()));
+  if (gg_status st = B->send.reserve(slots)) return st;
+  if (gg_status st = B->recv.reserve(slots)) return st;
+  if (gg_status st = B->dv.reserve(B->dv_words())) return st;
+  if (gg_status st = B->host.reserve(B->dv_words())) return st;
   // test knob: the first batches' step counts per rank ("n0,n1,...", rank r
   // takes entry r mod the list): a short first batch on one rank makes the
   // round repeat while the other ranks have finished the quantum

@@ -163,17 +163,13 @@ struct gg_stats_state {
   uint32_t statistics = 0;
   uint64_t interval_ns = 0, max_samples = 0;
   // of the run begun last (gg_stats_begin)
-  StatsDev D{};
-  uint64_t cap_words = 0;                // words allocated at D.samples
+  StatsDev D{};                          // (the view the kernels take: D.hdr / D.samples point into the two below)
+  gg_dbuf<unsigned long long> hdr, samples;
 };
 
 void gg_stats_free(gg_ctx* ctx)
 {
-  gg_stats_state* st = ctx->stats;
-  if (!st) return;
-  if (st->D.hdr) hipFree(st->D.hdr);
-  if (st->D.samples) hipFree(st->D.samples);
-  delete st;
+  delete ctx->stats;
   ctx->stats = nullptr;
 }
 
@@ -220,14 +216,11 @@ gg_status gg_stats_begin(gg_ctx* ctx, hipStream_t s)
   D.quantum_ns = ctx->cfg.quantum_ns;
   D.stride = GG_NUM_ST_FIELDS + ctx->cfg.num_tiles + 1;
   if (!D.statistics) return GG_OK;
-  if (!D.hdr) GG_HIP(hipMalloc((void**)&D.hdr, sizeof(unsigned long long) * SH_N));
   const uint64_t words = D.max_samples * D.stride;
-  if (words > st->cap_words) {
-    if (D.samples) GG_HIP(hipFree(D.samples));
-    D.samples = nullptr; st->cap_words = 0;
-    GG_HIP(hipMalloc((void**)&D.samples, sizeof(unsigned long long) * words));
-    st->cap_words = words;
-  }
+  D.hdr = D.samples = nullptr;
+  if (gg_status e = st->hdr.reserve(SH_N)) return e;
+  if (gg_status e = st->samples.reserve(words)) return e;
+  D.hdr = st->hdr.get(); D.samples = st->samples.get();
   GG_HIP(hipMemsetAsync(D.hdr, 0, sizeof(unsigned long long) * SH_N, s));
   GG_HIP(hipMemsetAsync(D.samples, 0, sizeof(unsigned long long) * words, s));
   return GG_OK;
