@@ -157,7 +157,10 @@ constexpr uint32_t kChunks = 128;      // record chunks per tile step
 constexpr uint32_t kChunk = 16;        // records per chunk
 constexpr uint32_t kQMax = 128;        // largest max_list_size of a queue staged in LDS (wave ops: 2 per lane)
 constexpr uint32_t kNetCtr = 7;        // router / link counters a walker accumulates per position
-constexpr size_t kWalkLdsMax = 160 * 1024;
+// the walkers' dynamic LDS: the CU's 160 KB less room for the static LDS of
+// the kernels that run walk_body (16 B in the persistent ones; a request for
+// static + dynamic past 160 KB is refused at set-up)
+constexpr size_t kWalkLdsMax = 160 * 1024 - 64;
 constexpr uint32_t kWalkPkBytes = 5 * 8 + 7 * 4;   // t, send, key, zl, queue t | idx, pos, dpos, nf/status, rank, queue rank, queue slot
 
 struct CP {
@@ -3618,6 +3621,9 @@ constexpr uint32_t kMaxWalkWaves = 16;
 #ifndef GG_WALK_SLEEP
 #define GG_WALK_SLEEP 1                              // s_sleep units (64 cycles) between polls of the packet words
 #endif
+#ifndef GG_WALK_ARM_SLEEP
+#define GG_WALK_ARM_SLEEP GG_WALK_SLEEP              // the same between polls of an armed wave (one word)
+#endif
 
 __device__ __forceinline__ uint64_t wave_min64(uint64_t v)
 {
@@ -3716,7 +3722,9 @@ __device__ __forceinline__ void walk_body(const CP& P, const CS& S, uint32_t L, 
   PROF_T0();
   if (n0 == 0) return;
   const uint32_t n = min(n0, P.seg_cap);
-  const uint32_t dir = sg & 1u;
+  // (wave-uniform, but sg comes out of a vector division: into an SGPR, so that
+  // what it steers — positions, bounds, the next router — stays scalar)
+  const uint32_t dir = (uint32_t)__builtin_amdgcn_readfirstlane((int)(sg & 1u));
   const int port = stage == 0 ? (dir ? P_RIGHT : P_LEFT) : (dir ? P_UP : P_DOWN);
   auto tile_at = [&](uint32_t pos) -> uint32_t { return stage == 0 ? sd.line * P.mw + pos : pos * P.mw + sd.line; };
   auto pos_of = [&](uint32_t tile) -> uint32_t { return stage == 0 ? tile % P.mw : tile / P.mw; };
@@ -3914,13 +3922,16 @@ __device__ __forceinline__ void walk_body(const CP& P, const CS& S, uint32_t L, 
     // ---- one wave per position (blockDim.x = 64 x positions): the pipeline
     // (n <= 128: lane l watches packets l and l + 64 if their route crosses
     // this port; the wide case took the sweep above)
-    const uint32_t pos = dir ? sd.lo + wv : sd.hi - wv;
+    // (wave-uniform, but computed from loaded values: into SGPRs, so that the
+    // armed poll's compares and everything they steer stay scalar)
+    const uint32_t pos = (uint32_t)__builtin_amdgcn_readfirstlane((int)(dir ? sd.lo + wv : sd.hi - wv));
     const uint32_t nx = dir ? pos + 1 : pos - 1;
     constexpr uint64_t kInf = ~0ull;
     const bool visited = lo <= hi && pos >= lo && pos <= hi;
     HTree tr;
     if (visited && !direct) port_queue(pos, rq, tr);
-    const uint32_t status_nx = (nx < sd.lo || nx > sd.hi) ? 2u : 0u;   // next router in another shard: held
+    const uint32_t status_nx =                                         // next router in another shard: held
+        (uint32_t)__builtin_amdgcn_readfirstlane((int)((nx < sd.lo || nx > sd.hi) ? 2u : 0u));
     const uint64_t zk = zps << 12;                                     // a port's router + link delay, in keys
     uint64_t cq = 0, cf = 0, m = 0;
     uint32_t spin = 0, polls = 0;
@@ -3943,12 +3954,24 @@ __device__ __forceinline__ void walk_body(const CP& P, const CS& S, uint32_t L, 
     uint32_t go = visited ? 1u : 0u;
     uint64_t l0 = kInf, l1 = kInf;                    // the candidates' words at the last evaluation
     bool waiting = false;
+    uint32_t d_arm = 0, d_hit = 0, d_cont = 0, d_miss = 0;   // armed waits by outcome (diagnostics)
+    auto rec_ev = [&](uint64_t ev0, uint64_t evp, uint64_t ev1, uint32_t i, uint32_t npoll) {
+      if (ln != 0) return;
+      const uint32_t k = atomicAdd(reinterpret_cast<unsigned int*>(&rlohi[2]), 1u);
+      if (k < kTrEvMax) {
+        unsigned long long* e = tre + 4 + 4 * k;
+        e[0] = ev0; e[1] = evp; e[2] = ev1;
+        e[3] = (unsigned long long)i | ((unsigned long long)pos << 16) | ((unsigned long long)wv << 24) |
+               ((unsigned long long)npoll << 32);
+      }
+    };
     while (__builtin_amdgcn_readfirstlane((int)go)) {
       // the candidates' packet words: the only signal between the waves (a
       // forward is one relaxed atomic store of the word; nothing else travels
       // with it).  A waiting wave re-evaluates only when one of them moved:
       // its decision depends on nothing else (the cheap poll keeps the waiting
-      // waves off the serving waves' issue slots)
+      // waves off the serving waves' issue slots).  With register queues the
+      // wave waits armed instead (below) and never comes back here waiting
       const uint64_t w0 = c0 ? lds_load_rlx(&W.Qt[ln]) : kInf;
       const uint64_t w1 = c1 ? lds_load_rlx(&W.Qt[ln + 64]) : kInf;
       if (waiting && !__ballot(w0 != l0 || w1 != l1)) {
@@ -3964,12 +3987,12 @@ __device__ __forceinline__ void walk_body(const CP& P, const CS& S, uint32_t L, 
       // a packet arrives here no earlier than tt + d * zps (every port adds
       // zps and a queue delay >= 0).  A stale word only gives a smaller bound.
       uint64_t mk = kInf, bk = kInf;
-      uint32_t mi = 0, mfd = 0;
+      uint32_t mi = 0, mfd = 0, bi = 0, bfd = 0;      // (bi, bfd: the packet of bk, for arming)
       if (c0) {
         const uint32_t pp = pipe_pos(w0);
         const uint64_t k = (w0 & ~0xFFFull) | r0;
         if (pp == pos) { mk = k; mi = ln; mfd = fd0; }
-        else bk = k + (uint64_t)(dir ? pos - pp : pp - pos) * zk;
+        else { bk = k + (uint64_t)(dir ? pos - pp : pp - pos) * zk; bi = ln; bfd = fd0; }
       }
       if (c1) {
         const uint32_t pp = pipe_pos(w1);
@@ -3978,7 +4001,7 @@ __device__ __forceinline__ void walk_body(const CP& P, const CS& S, uint32_t L, 
           if (k < mk) { mk = k; mi = ln + 64; mfd = fd1; }
         } else {
           const uint64_t b = k + (uint64_t)(dir ? pos - pp : pp - pos) * zk;
-          bk = b < bk ? b : bk;
+          if (b < bk) { bk = b; bi = ln + 64; bfd = fd1; }
         }
       }
       // the least pending key: a scalar pass over the lanes holding one
@@ -3993,49 +4016,113 @@ __device__ __forceinline__ void walk_body(const CP& P, const CS& S, uint32_t L, 
       // key (keys are unique); no candidate left at all: this port is done
       const uint64_t below = __ballot(bk < wk);
       if (wk == kInf && !below) { go = 0; continue; }
+      // the serve: packet i, nf flits, at cycle tc with queue delay qd
+      uint32_t i = 0, nf = 0;
+      uint64_t tc = 0, qd = 0, ev0 = 0, evp = 0;
+      RegQueue::Found fs{0ull, 0u, RegQueue::kNone};
       if (below) {
         if (++spin > (1u << 22)) { if (ln == 0) atomicOr(S.err, GG_DERR_STATE); go = 0; continue; }
         ++polls;
-        waiting = true;
-        __builtin_amdgcn_s_sleep(GG_WALK_SLEEP);
-        continue;
+        if constexpr (RQ) {
+          // ---- arm: the wave knows which packet it waits for and when that
+          // packet can arrive, so it prepares that serve before it sleeps.
+          // c* is the upstream candidate with the least bound key bs (a scalar
+          // pass over the lanes in `below`).  If c* arrives here at its bound
+          // — its word becomes (bs >> 12, pos, 0) — the serve is the request
+          // (time_to_cycles(bs >> 12), c*'s flits), whose search runs now; the
+          // armed wave then polls c*'s word only and on a hit stores the
+          // prepared forward word at once, the queue's update after it.
+          // Exact: on a hit c*'s key here is bs, and bs was below the least
+          // pending key wk.  Every other upstream candidate's bound was above
+          // bs at arming (bs is the least; ranks make keys unique), and bounds
+          // only grow: a word only moves forward in time and position, each
+          // port adding at least zps.  A candidate that became pending here
+          // meanwhile has a key at or above its old bound, so above bs.  The
+          // queue has not changed since arming but for the prune, which the
+          // next request does first whichever packet it serves.  So the port
+          // sees the same request at the same place in the canonical order as
+          // after a full evaluation, and no other candidate's word needs a
+          // look while the wave is armed.  A word of c* that still implies bs
+          // (it advanced a port with no delay) keeps the wave waiting; any
+          // other word means c* was delayed upstream: the bound grew, the
+          // wave disarms and evaluates every candidate again.
+          uint64_t bs = kInf;
+          uint32_t bl = 0;
+          for (uint64_t bm = below; bm; bm &= bm - 1) {
+            const uint32_t l = (uint32_t)__builtin_ctzll(bm);
+            const uint64_t k = rl64(bk, l);
+            if (k < bs) { bs = k; bl = l; }
+          }
+          const uint32_t ci = (uint32_t)__builtin_amdgcn_readlane((int)bi, (int)bl);
+          const uint32_t cfd = (uint32_t)__builtin_amdgcn_readlane((int)bfd, (int)bl);
+          const uint32_t cr = (uint32_t)bs & 0xFFFu, nf_ = cfd & 0xFFFFFFu;
+          const uint64_t Tc = bs >> 12;
+          const uint64_t pred = pipe_word(Tc, pos, 0u);
+          const uint32_t status = status_nx ? status_nx : (nx == (cfd >> 24) ? 1u : 0u);
+          rq.prune();
+          const uint64_t tc_ = rfl64(time_to_cycles(Tc, P.np.f));
+          fs = rq.search(tc_, nf_);
+          fs.qd = rfl64(fs.qd);
+          const uint64_t fwd = pipe_word(Tc + zps + rfl64(lat_to_ps(fs.qd, P.np.f)), nx, status);
+          uint64_t seen = GG_COH_DIAG ? rl64(ci < 64 ? w0 : w1, bl) : 0;
+          if (GG_COH_DIAG) ++d_arm;
+          // ---- armed poll: one LDS load
+          bool hit = false;
+          for (;;) {
+            const uint64_t w = rfl64(lds_load_rlx(&W.Qt[ci]));
+            if (w == pred) { hit = true; break; }
+            const uint32_t pp = pipe_pos(w);
+            const uint64_t b = ((w & ~0xFFFull) | cr) + (uint64_t)(dir ? pos - pp : pp - pos) * zk;
+            if (b != bs) break;
+            if (GG_COH_DIAG && w != seen) { seen = w; ++d_cont; }
+            if (++spin > (1u << 22)) { if (ln == 0) atomicOr(S.err, GG_DERR_STATE); go = 0; break; }
+            __builtin_amdgcn_s_sleep(GG_WALK_ARM_SLEEP);
+          }
+          if (!hit) { if (GG_COH_DIAG) ++d_miss; continue; }
+          // the prepared forward, then the queue's update below
+          if (GG_COH_DIAG) ++d_hit;
+          ev0 = tev ? __builtin_amdgcn_s_memtime() : 0;
+          if (ln == 0) lds_store_rlx(&W.Qt[ci], fwd);
+          if (tev) evp = __builtin_amdgcn_s_memtime();
+          i = ci; nf = nf_; tc = tc_; qd = fs.qd;
+        } else {
+          waiting = true;
+          __builtin_amdgcn_s_sleep(GG_WALK_SLEEP);
+          continue;
+        }
+      } else {
+        const uint64_t T = wk >> 12;
+        ev0 = tev ? __builtin_amdgcn_s_memtime() : 0;
+        // serve it: the router + link (serve_packet's arithmetic); the packet
+        // moves downstream as soon as its queue delay is known, the port's
+        // queue is updated after that (RegQueue: search, forward, apply)
+        i = (uint32_t)__builtin_amdgcn_readlane((int)mi, (int)wl);
+        const uint32_t fd = (uint32_t)__builtin_amdgcn_readlane((int)mfd, (int)wl);
+        nf = fd & 0xFFFFFFu;
+        const uint32_t status = status_nx ? status_nx : (nx == (fd >> 24) ? 1u : 0u);   // 1: leaves the run
+        auto pub = [&](uint64_t qd) {
+          if (tev) evp = __builtin_amdgcn_s_memtime();
+          // the forward: the packet word (time, next position, status; the
+          // zero-load part, + zps per port, is added at the hand-off)
+          if (ln == 0) lds_store_rlx(&W.Qt[i], pipe_word(T + zps + lat_to_ps(qd, P.np.f), nx, status));
+        };
+        if (!qm) pub(0ull);
+        else {
+          tc = rfl64(time_to_cycles(T, P.np.f));
+          if (regq) { rq.prune(); fs = rq.search(tc, nf); qd = fs.qd; pub(qd); }
+          else { qd = wave_q ? tr.delay_w(tc, nf, S.err, ln) : tr.delay(tc, nf, S.err); pub(qd); }
+        }
       }
-      const uint64_t T = wk >> 12;
-      const uint64_t ev0 = tev ? __builtin_amdgcn_s_memtime() : 0;
-      // serve it: the router + link (serve_packet's arithmetic); the packet
-      // moves downstream as soon as its queue delay is known, the port's
-      // queue is updated after that (request_pub)
-      const uint32_t i = (uint32_t)__builtin_amdgcn_readlane((int)mi, (int)wl);
-      const uint32_t fd = (uint32_t)__builtin_amdgcn_readlane((int)mfd, (int)wl);
-      const uint32_t nf = fd & 0xFFFFFFu;
-      const uint32_t status = status_nx ? status_nx : (nx == (fd >> 24) ? 1u : 0u);   // 1: leaves the run
-      uint64_t evp = 0;
-      auto pub = [&](uint64_t qd) {
-        if (tev) evp = __builtin_amdgcn_s_memtime();
-        // the forward: the packet word (time, next position, status; the
-        // zero-load part, + zps per port, is added at the hand-off)
-        if (ln == 0) lds_store_rlx(&W.Qt[i], pipe_word(T + zps + lat_to_ps(qd, P.np.f), nx, status));
-      };
-      uint64_t qd = 0;
-      if (!qm) pub(0ull);
-      else {
-        const uint64_t tc = rfl64(time_to_cycles(T, P.np.f));
-        if (regq) qd = rq.request_pub(tc, nf, pub);
-        else { qd = wave_q ? tr.delay_w(tc, nf, S.err, ln) : tr.delay(tc, nf, S.err); pub(qd); }
-      }
+      if (regq) rq.apply(tc, nf, fs);
       const uint64_t ev1 = tev ? __builtin_amdgcn_s_memtime() : 0;
       cq += qd; cf += nf; ++m;
       if (ln == (i & 63)) { if (i < 64) c0 = false; else c1 = false; }   // served here: no longer a candidate
-      if (tev && ln == 0) {
-        const uint32_t k = atomicAdd(reinterpret_cast<unsigned int*>(&rlohi[2]), 1u);
-        if (k < kTrEvMax) {
-          unsigned long long* e = tre + 4 + 4 * k;
-          e[0] = ev0; e[1] = evp; e[2] = ev1;
-          e[3] = (unsigned long long)i | ((unsigned long long)pos << 16) | ((unsigned long long)wv << 24) |
-                 ((unsigned long long)polls << 32);
-        }
-      }
+      if (tev) rec_ev(ev0, evp, ev1, i, polls);
       wave_sync();
+    }
+    if (RQ && DG(S.prof) && ln == 0 && d_arm) {
+      atomicAdd(&DG(S.prof)[100], (unsigned long long)d_arm); atomicAdd(&DG(S.prof)[101], (unsigned long long)d_hit);
+      atomicAdd(&DG(S.prof)[102], (unsigned long long)d_cont); atomicAdd(&DG(S.prof)[103], (unsigned long long)d_miss);
     }
     if (regq && visited && direct && m) {
       const uint64_t qi = (uint64_t)tile_at(pos) * 6 + port;

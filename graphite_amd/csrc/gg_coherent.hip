@@ -1135,6 +1135,9 @@ static gg_status coh_drive(gg_ctx* ctx, bool may_persist, uint64_t* done_out)
       fprintf(stderr, "[gg_coh] per-launch max requests summed: tile (self+sent) %llu walker X %llu Y %llu\n", mt, mx, my);
       fprintf(stderr, "[gg_coh] walkers: most packets in one run X %llu Y %llu; pipelined runs past 64 packets (a lane's second "
               "candidate; past 128 wave 0 sweeps) %llu\n", h[46], h[47], h[48]);
+      fprintf(stderr, "[gg_coh] walkers, armed waits: arms %llu hits %llu (%.1f %% of %llu serves) misses %llu; "
+              "same-bound continues %llu\n", h[100], h[101], h[19] ? 100.0 * (double)h[101] / (double)h[19] : 0.0, h[19],
+              h[103], h[102]);
       unsigned long long sn = 0, sa = 0, ss = 0, c1 = 0, c2 = 0, c3 = 0, ct = 0, nl = 0;
       for (int i = 0; i < 16384; ++i) {
         const unsigned long long* b = &h[1024 + 6 * 65536 + 4 * i];

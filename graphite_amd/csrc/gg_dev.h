@@ -678,34 +678,53 @@ struct RegQueue {
     ++total_req;
     return qd;
   }
-  // The same request with the delay handed to pub(qd) as soon as it is
-  // known, before the interval list and the M/G/1 sums are updated: a
-  // pipeline stage forwards its packet first and does the bookkeeping while
-  // the next stage runs (this queue's next request comes from the same wave,
-  // after it).  One vector search serves every case (no last-interval
-  // pre-check: the walkers' requests land mid-list, and the last interval
-  // [x, inf) is found by the same compares): the interval holding t fits
-  // [t, t+p] -> no delay, published after two compares; otherwise either the
-  // analytical branch (interval 0 starts after t + p; never with a fit, whose
-  // interval starts at or before t) or the first later interval long enough.
-  // Uniform values are kept scalar (readfirstlane) so a loop around it
-  // carries them in SGPRs.
+  // The same request in halves, for a pipeline stage that forwards its packet
+  // as soon as the delay is known and does the bookkeeping while the next
+  // stage runs (this queue's next request comes from the same wave, after
+  // it).  prune() is what every request does first; search() only reads the
+  // queue and gives the delay and the interval that serves [t, t+p]; apply()
+  // updates the interval list and the M/G/1 sums with that result.  Nothing
+  // touches the queue between the halves, so prune, search ... apply is the
+  // request made at the time of apply(): a wave that knows its next request
+  // ahead of the packet's arrival runs prune() and search() while it waits.
+  // One vector search serves every case (no last-interval pre-check: the
+  // walkers' requests land mid-list, and the last interval [x, inf) is found
+  // by the same compares): the interval holding t fits [t, t+p] -> no delay,
+  // known after two compares; otherwise either the analytical branch
+  // (interval 0 starts after t + p; never with a fit, whose interval starts at
+  // or before t) or the first later interval long enough.  Uniform values are
+  // kept scalar (readfirstlane) so a loop around it carries them in SGPRs.
   __device__ __forceinline__ uint64_t rd64(uint64_t v) const { return rfl64(v); }
   __device__ __forceinline__ uint64_t A1(uint32_t i) const { return i < 64 ? rl64(a0, i) : rl64(a1, i - 64); }
   __device__ __forceinline__ uint64_t B1(uint32_t i) const { return i < 64 ? rl64(b0, i) : rl64(b1, i - 64); }
-  template <class Pub>
-  __device__ __forceinline__ uint64_t request_pub(uint64_t t, uint64_t p, Pub&& pub)
+  enum : uint32_t { kFit = 0, kAnalytical = 1, kLater = 2, kNone = 3 };
+  struct Found { uint64_t qd; uint32_t ui, kind; };
+  __device__ __forceinline__ void prune()
   {
     if (sz >= cap) { shift_down(0); --sz; }                          // prune the min node (:52-56)
-    uint64_t qd = 0;
+  }
+  __device__ __forceinline__ Found search(uint64_t t, uint64_t p) const
+  {
     const uint64_t tp = t + p;
     const uint64_t v0 = low_lanes(sz), v1 = sz > 64 ? low_lanes(sz - 64) : 0ull;
     const uint64_t le0 = cmp64<kCmpULE>(a0, t) & v0, le1 = cmp64<kCmpULE>(a1, t) & v1;
     const uint64_t f0 = le0 & cmp64<kCmpUGE>(b0, tp), f1 = le1 & cmp64<kCmpUGE>(b1, tp);
-    if (f0 | f1) {                                                   // a <= t, t + p <= b: no delay
-      pub(0ull);
+    if (f0 | f1)                                                     // a <= t, t + p <= b: no delay
+      return Found{0ull, f0 ? (uint32_t)__builtin_ctzll(f0) : 64u + (uint32_t)__builtin_ctzll(f1), kFit};
+    if (analytical && (cmp64<kCmpUGT>(a0, tp) & 1ull))               // interval 0 starts after t + p
+      return Found{rd64(mg1_queue_delay(nreq, newest, sig_sq, sig)), 0u, kAnalytical};
+    const uint64_t m0 = ~le0 & v0 & cmp64<kCmpUGE>(b0 - a0, p);      // the first later interval long enough
+    const uint64_t m1 = ~le1 & v1 & cmp64<kCmpUGE>(b1 - a1, p);
+    if ((m0 | m1) == 0) return Found{0ull, 0u, kNone};
+    const uint32_t ui = m0 ? (uint32_t)__builtin_ctzll(m0) : 64u + (uint32_t)__builtin_ctzll(m1);
+    return Found{A1(ui) - t, ui, kLater};
+  }
+  __device__ __forceinline__ void apply(uint64_t t, uint64_t p, const Found& s)
+  {
+    const uint64_t tp = t + p, qd = s.qd;
+    const uint32_t ui = s.ui;
+    if (s.kind == kFit) {
       ++n_gen;
-      const uint32_t ui = f0 ? (uint32_t)__builtin_ctzll(f0) : 64u + (uint32_t)__builtin_ctzll(f1);
       const uint64_t a = A1(ui), b = B1(ui);
       if (t - a >= min_proc) {
         if (b - tp >= min_proc) { shift_up(ui + 1); set(ui + 1, tp, b); ++sz; }
@@ -715,26 +734,16 @@ struct RegQueue {
       } else {
         shift_down(ui); --sz;
       }
-    } else if (analytical && (cmp64<kCmpUGT>(a0, tp) & 1ull)) {     // interval 0 starts after t + p
-      qd = mg1_queue_delay(nreq, newest, sig_sq, sig);
-      pub(qd);
+    } else if (s.kind == kAnalytical) {
       ++anl; ++n_anl;
-    } else {                                                         // the first later interval long enough
+    } else if (s.kind == kNone) {
       ++n_gen;
-      const uint64_t m0 = ~le0 & v0 & cmp64<kCmpUGE>(b0 - a0, p);
-      const uint64_t m1 = ~le1 & v1 & cmp64<kCmpUGE>(b1 - a1, p);
-      if ((m0 | m1) == 0) {
-        pub(0ull);
-        errs |= GG_DERR_STATE;
-      } else {
-        const uint32_t ui = m0 ? (uint32_t)__builtin_ctzll(m0) : 64u + (uint32_t)__builtin_ctzll(m1);
-        const uint64_t a = A1(ui);
-        qd = a - t;
-        pub(qd);
-        const uint64_t b = B1(ui);
-        if (b - (a + p) >= min_proc) set(ui, a + p, b);
-        else { shift_down(ui); --sz; }
-      }
+      errs |= GG_DERR_STATE;
+    } else {
+      ++n_gen;
+      const uint64_t a = A1(ui), b = B1(ui);
+      if (b - (a + p) >= min_proc) set(ui, a + p, b);
+      else { shift_down(ui); --sz; }
     }
     sig_sq = rd64(sig_sq + p * p);                                   // QueueModelMG1::updateQueue
     sig = rd64(sig + p);
@@ -747,7 +756,6 @@ struct RegQueue {
     total_req = rd64(total_req + 1);
     anl = rd64(anl);
     sz = (uint32_t)__builtin_amdgcn_readfirstlane((int)sz);
-    return qd;
   }
 };
 
