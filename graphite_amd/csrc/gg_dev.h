@@ -418,15 +418,20 @@ struct HTree {
 
 // ---------------------------------------------------------------------------
 // One history-tree queue held in a wave's registers for a batch of requests
-// (every lane calls every method with identical arguments).  Logical interval
-// i (< 128 = max_size bound) sits in lane i & 63 of slot i >> 6, so the
-// queue's state costs no memory round trip per request: the search is two
-// ballots, an insert / erase a one-lane shift of the slots (DPP wave_shr /
-// wave_shl), the header and M/G/1 sums are uniform registers.  load / store
-// move the image (HQueue + circular node list, any head) in one round each;
-// store writes it back with head 0.  Same request as HTree::tree_delay +
-// mg1_update (the in-order request, t at or after the start of the last
-// interval [x, UINT64_MAX), is the O(1) first branch).
+// (every lane calls every method with identical arguments).  The 128 register
+// positions (position x = lane x & 63 of slot x >> 6; 128 = max_size bound)
+// form a ring: logical interval i sits at position (hd + i) & 127, hd a
+// uniform scalar, so pruning the oldest interval of a full list is hd + 1 and
+// moves no lane.  The queue's state costs no memory round trip per request:
+// the search is two ballots over the ring range [hd, hd + sz), an insert /
+// erase a one-position rotate of both slots (DPP wave_ror / wave_rol, lane 0 /
+// 63 taking the other slot's value) masked by the lanes' logical index, the
+// header and M/G/1 sums are uniform registers.  load / store move the image
+// (HQueue + circular node list, any head) in one round each: load brings the
+// list into logical order (hd = 0), store writes it back in logical order
+// with head 0.  Same request as HTree::tree_delay + mg1_update (the in-order
+// request, t at or after the start of the last interval [x, UINT64_MAX), is
+// the O(1) first branch).
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ uint64_t rl64(uint64_t v, uint32_t l)
 {
@@ -440,14 +445,21 @@ __device__ __forceinline__ uint64_t rfl64(uint64_t v)
   return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
          (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
 }
-template <int CTRL> __device__ __forceinline__ uint64_t dpp64(uint64_t v)
+// v shifted by SHIFT (a wave shift: one lane has no source) over w rotated by
+// ROT (every lane has one), so the lane without a source takes w's
+template <int SHIFT, int ROT> __device__ __forceinline__ uint32_t dpp32(uint32_t v, uint32_t w)
 {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)v, (int)(uint32_t)v, CTRL, 0xf, 0xf, false);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)(v >> 32), (int)(uint32_t)(v >> 32), CTRL, 0xf, 0xf, false);
-  return ((uint64_t)hi << 32) | lo;
+  const int r = __builtin_amdgcn_mov_dpp((int)w, ROT, 0xf, 0xf, false);
+  return (uint32_t)__builtin_amdgcn_update_dpp(r, (int)v, SHIFT, 0xf, 0xf, false);
 }
-constexpr int kDppWaveShl1 = 0x130;    // lane l <- lane l + 1
-constexpr int kDppWaveShr1 = 0x138;    // lane l <- lane l - 1
+template <int SHIFT, int ROT> __device__ __forceinline__ uint64_t dpp64(uint64_t v, uint64_t w)
+{
+  return ((uint64_t)dpp32<SHIFT, ROT>((uint32_t)(v >> 32), (uint32_t)(w >> 32)) << 32) | dpp32<SHIFT, ROT>((uint32_t)v, (uint32_t)w);
+}
+constexpr int kDppWaveShl1 = 0x130;    // lane l <- lane l + 1, lane 63 keeps `old`
+constexpr int kDppWaveRol1 = 0x134;    // lane l <- lane (l + 1) & 63
+constexpr int kDppWaveShr1 = 0x138;    // lane l <- lane l - 1, lane 0 keeps `old`
+constexpr int kDppWaveRor1 = 0x13C;    // lane l <- lane (l - 1) & 63
 
 // lane mask of a 64-bit comparison (one v_cmp into an SGPR pair, no bool
 // materialization between compare and ballot)
@@ -455,12 +467,17 @@ template <int PRED> __device__ __forceinline__ uint64_t cmp64(uint64_t a, uint64
 {
   return __builtin_amdgcn_uicmpl(a, b, PRED);
 }
-constexpr int kCmpULE = 37, kCmpUGE = 35, kCmpUGT = 34;     // ICmpInst predicates
+template <int PRED> __device__ __forceinline__ uint64_t cmp32(uint32_t a, uint32_t b)
+{
+  return __builtin_amdgcn_uicmp(a, b, PRED);
+}
+constexpr int kCmpULE = 37, kCmpULT = 36, kCmpUGE = 35, kCmpUGT = 34;     // ICmpInst predicates
 __device__ __forceinline__ uint64_t low_lanes(uint32_t n) { return n >= 64 ? ~0ull : ((1ull << n) - 1); }
 
 struct RegQueue {
   uint64_t a0, b0, a1, b1;             // this lane's intervals of slot 0 / slot 1
   uint32_t sz, cap, ln;
+  uint32_t hd = 0;                     // position of logical interval 0 (uniform)
   uint64_t sig_sq, sig, nreq, newest, util, last_req, total_req, anl;
   uint64_t min_proc;
   bool analytical;
@@ -473,7 +490,7 @@ struct RegQueue {
     // the header is wave-uniform: into SGPRs (a load from memory the kernel
     // also writes lands in VGPRs, and the size would then steer every request
     // through exec-masked branches)
-    ln = lane; min_proc = mp; analytical = an; errs = 0; errp = nullptr;
+    ln = lane; min_proc = mp; analytical = an; errs = 0; errp = nullptr; hd = 0;
     sz = (uint32_t)__builtin_amdgcn_readfirstlane((int)q->size);
     cap = (uint32_t)__builtin_amdgcn_readfirstlane((int)q->max_size);
     const uint32_t head = (uint32_t)__builtin_amdgcn_readfirstlane((int)q->head);
@@ -499,7 +516,7 @@ struct RegQueue {
     if (lane + 64 < max_size) x1 = nd[lane + 64];
     const uint32_t h = (uint32_t)__builtin_amdgcn_readfirstlane((int)q->head);
     if (h != 0) { load(q, nd, mp, an, lane); return; }
-    ln = lane; min_proc = mp; analytical = an; errs = 0; errp = nullptr;
+    ln = lane; min_proc = mp; analytical = an; errs = 0; errp = nullptr; hd = 0;
     sz = (uint32_t)__builtin_amdgcn_readfirstlane((int)q->size);
     cap = (uint32_t)__builtin_amdgcn_readfirstlane((int)q->max_size);
     sig_sq = rfl64(q->sig_sq); sig = rfl64(q->sig); nreq = rfl64(q->n); newest = rfl64(q->newest);
@@ -541,7 +558,7 @@ struct RegQueue {
   {
     const uint32_t h = hw32<offsetof(HQueue, head)>(r.hc);
     if (h != 0) { load(q, nd, mp, an, lane); return; }
-    ln = lane; min_proc = mp; analytical = an; errs = 0; errp = nullptr;
+    ln = lane; min_proc = mp; analytical = an; errs = 0; errp = nullptr; hd = 0;
     sz = hw32<offsetof(HQueue, size)>(r.hc);
     cap = hw32<offsetof(HQueue, max_size)>(r.hc);
     sig_sq = hw64<offsetof(HQueue, sig_sq)>(r.hc); sig = hw64<offsetof(HQueue, sig)>(r.hc);
@@ -555,207 +572,229 @@ struct RegQueue {
   __device__ __forceinline__ void store(HQueue* q, HNode* nd) const
   {
     if (errs && errp && ln == 0) atomicOr(errp, errs);
-    if (ln < sz) nd[ln] = HNode{a0, b0};
-    if (ln + 64 < sz) nd[ln + 64] = HNode{a1, b1};
+    const uint32_t l0 = li(), l1 = l0 ^ 64u;
+    if (l0 < sz) nd[l0] = HNode{a0, b0};
+    if (l1 < sz) nd[l1] = HNode{a1, b1};
     q->size = sz; q->head = 0;
     q->sig_sq = sig_sq; q->sig = sig; q->n = nreq; q->newest = newest;
     q->util = util; q->last_req = last_req; q->total_req = total_req; q->analytical = anl;
   }
-  // interval i's bounds: both slots read, then a scalar select (no branch)
-  __device__ __forceinline__ uint64_t A(uint32_t i) const
+  // this lane's logical index in slot 0 (slot 1: the same ^ 64), and the
+  // position of logical interval i
+  __device__ __forceinline__ uint32_t li() const { return (ln - hd) & 127u; }
+  __device__ __forceinline__ uint32_t pos(uint32_t i) const { return (hd + i) & 127u; }
+  // the bounds at position x: both slots read, then a scalar select (no branch)
+  __device__ __forceinline__ uint64_t PA(uint32_t x) const
   {
-    const uint32_t l = i & 63; const uint64_t u = rl64(a0, l), v = rl64(a1, l); return i < 64 ? u : v;
+    const uint32_t l = x & 63; const uint64_t u = rl64(a0, l), v = rl64(a1, l); return x < 64 ? u : v;
   }
-  __device__ __forceinline__ uint64_t B(uint32_t i) const
+  __device__ __forceinline__ uint64_t PB(uint32_t x) const
   {
-    const uint32_t l = i & 63; const uint64_t u = rl64(b0, l), v = rl64(b1, l); return i < 64 ? u : v;
+    const uint32_t l = x & 63; const uint64_t u = rl64(b0, l), v = rl64(b1, l); return x < 64 ? u : v;
   }
+  // logical interval i's bounds
+  __device__ __forceinline__ uint64_t A(uint32_t i) const { return PA(pos(i)); }
+  __device__ __forceinline__ uint64_t B(uint32_t i) const { return PB(pos(i)); }
   __device__ __forceinline__ void set(uint32_t i, uint64_t a, uint64_t b)
   {
-    if ((i & 63) == ln) { if (i < 64) { a0 = a; b0 = b; } else { a1 = a; b1 = b; } }
+    const uint32_t x = pos(i);
+    if ((x & 63) == ln) { if (x < 64) { a0 = a; b0 = b; } else { a1 = a; b1 = b; } }
   }
-  // new[x] = old[x - 1] for x > k
-  __device__ __forceinline__ void shift_up(uint32_t k)
+  // One-position rotates over the 128 positions, masked by the lanes' logical
+  // index.  The wave shift leaves the lane without a source (0 going up, 63
+  // going down) at the `old` operand, which is the other slot rotated: that
+  // lane so takes the other slot's end, which carries slot 0 lane 63 <-> slot 1
+  // lane 0 and closes the ring, slot 1 lane 63 <-> slot 0 lane 0.
+  // up: new[i] = old[i - 1] for logical i with m0 / m1 set (slot 0 / 1)
+  __device__ __forceinline__ void rotate_up(bool m0, bool m1)
   {
-    const uint64_t ca = rl64(a0, 63), cb = rl64(b0, 63);
-    const uint64_t pa0 = dpp64<kDppWaveShr1>(a0), pb0 = dpp64<kDppWaveShr1>(b0);
-    const uint64_t pa1 = dpp64<kDppWaveShr1>(a1), pb1 = dpp64<kDppWaveShr1>(b1);
-    if (ln > k) { a0 = pa0; b0 = pb0; }
-    if (ln + 64 > k) { a1 = ln == 0 ? ca : pa1; b1 = ln == 0 ? cb : pb1; }
+    const uint64_t pa0 = dpp64<kDppWaveShr1, kDppWaveRor1>(a0, a1), pa1 = dpp64<kDppWaveShr1, kDppWaveRor1>(a1, a0);
+    a0 = m0 ? pa0 : a0; a1 = m1 ? pa1 : a1;
+    __builtin_amdgcn_sched_barrier(0);               // starts, then ends: four temporaries live, not eight
+    const uint64_t pb0 = dpp64<kDppWaveShr1, kDppWaveRor1>(b0, b1), pb1 = dpp64<kDppWaveShr1, kDppWaveRor1>(b1, b0);
+    b0 = m0 ? pb0 : b0; b1 = m1 ? pb1 : b1;
   }
-  // new[x] = old[x + 1] for x >= k
-  __device__ __forceinline__ void shift_down(uint32_t k)
+  // down: new[i] = old[i + 1]
+  __device__ __forceinline__ void rotate_down(bool m0, bool m1)
   {
-    const uint64_t ca = rl64(a1, 0), cb = rl64(b1, 0);
-    const uint64_t na0 = dpp64<kDppWaveShl1>(a0), nb0 = dpp64<kDppWaveShl1>(b0);
-    const uint64_t na1 = dpp64<kDppWaveShl1>(a1), nb1 = dpp64<kDppWaveShl1>(b1);
-    if (ln >= k) { a0 = ln == 63 ? ca : na0; b0 = ln == 63 ? cb : nb0; }
-    if (ln + 64 >= k) { a1 = na1; b1 = nb1; }
+    const uint64_t na0 = dpp64<kDppWaveShl1, kDppWaveRol1>(a0, a1), nb0 = dpp64<kDppWaveShl1, kDppWaveRol1>(b0, b1);
+    const uint64_t na1 = dpp64<kDppWaveShl1, kDppWaveRol1>(a1, a0), nb1 = dpp64<kDppWaveShl1, kDppWaveRol1>(b1, b0);
+    a0 = m0 ? na0 : a0; b0 = m0 ? nb0 : b0;
+    a1 = m1 ? na1 : a1; b1 = m1 ? nb1 : b1;
   }
-  // computeQueueDelay (queue_model_history_tree.cc:44-126) + QueueModelMG1::updateQueue.
-  // TAIL: also the O(1) branch for requests served by the last two intervals
-  // (in-order streams: SELF / injection ports); the walkers' requests land
-  // mid-list 84 % of the time and skip that check (TAIL = false: the general
-  // search serves those requests too, with the same result).
-  template <bool TAIL = true>
-  __device__ __forceinline__ uint64_t request(uint64_t t, uint64_t p, uint32_t* err)
+  // new[i] = old[i - 1] for i > k (logical 127, beyond any list here, is lost)
+  __device__ __forceinline__ void shift_up(uint32_t k) { const uint32_t l = li(); rotate_up(l > k, (l ^ 64u) > k); }
+  // new[i] = old[i + 1] for i >= k (logical 127 takes what was logical 0's position: not an interval)
+  __device__ __forceinline__ void shift_down(uint32_t k) { const uint32_t l = li(); rotate_down(l >= k, (l ^ 64u) >= k); }
+  // QueueModelMG1::updateQueue + updateQueueUtilizationCounters.  RB: the
+  // sums are read back into SGPRs (readfirstlane; they are uniform).  That
+  // pays where the loop around the request carries them in SGPRs (the step
+  // kernel's port batches: -1.5 % of k_c_step with it, +0.9 % without); the
+  // pipelined walker's loop joins branches on values loaded from memory and
+  // holds the sums in VGPRs whatever is done here, so a read-back there is 16
+  // readfirstlane and as many copies back a serve (-2.9 % of k_c_walk
+  // without it; profiles/r15).
+  template <bool RB> __device__ __forceinline__ static uint64_t rd64(uint64_t v) { return RB ? rfl64(v) : v; }
+  template <bool RB> __device__ __forceinline__ void account(uint64_t t, uint64_t p, uint64_t qd)
   {
-    errp = err;
-    if (sz >= cap) { shift_down(0); --sz; }                          // prune the min node (:52-56)
-    uint64_t qd = 0;
-    const uint64_t la = A(sz - 1), lb = B(sz - 1);
-    if (la <= t && t + p <= lb && lb - (t + p) >= min_proc) {        // the last interval: no search, no delay
-      ++n_fast;
-      if (t - la >= min_proc) { set(sz - 1, la, t); set(sz, t + p, lb); ++sz; }
-      else set(sz - 1, t + p, lb);
-    } else if (TAIL && sz >= 2 && t < la && t >= A(sz - 2)) {
-      // the tail: interval sz-2 is the last one starting at or before t (and
-      // interval 0 starts before t: no M/G/1).  Either [t, t+p] fits in it, or
-      // the first later interval long enough is the last one (unbounded)
-      ++n_fast;
-      const uint32_t i2 = sz - 2, i1 = sz - 1;
-      const uint64_t a2 = A(i2), b2 = B(i2);
-      if (t + p <= b2) {
-        if (t - a2 >= min_proc) {
-          if (b2 - (t + p) >= min_proc) { set(i1 + 1, la, lb); set(i1, t + p, b2); ++sz; }
-          set(i2, a2, t);
-        } else if (b2 - (t + p) >= min_proc) {
-          set(i2, t + p, b2);
-        } else {
-          set(i2, la, lb); --sz;                                       // erase interval sz-2
-        }
-      } else {
-        qd = la - t;                                                   // queued behind the busy period
-        if (lb - (la + p) >= min_proc) set(i1, la + p, lb);
-        else --sz;                                                     // erase the last interval
-      }
-    } else if (analytical && A(0) > t + p) {
-      ++anl; ++n_anl;
-      qd = mg1_queue_delay(nreq, newest, sig_sq, sig);
-    } else {
-      ++n_gen;
-      // fit: a <= t && t + p <= b — at most one interval (the intervals are
-      // disjoint and sorted: any earlier one ends before the last start <= t),
-      // the last one starting at or before t; else the first later one
-      // (a > t) with b - a >= p.  Lane masks straight from the compares.
-      const uint64_t tp = t + p;
-      const uint64_t v0 = low_lanes(sz), v1 = sz > 64 ? low_lanes(sz - 64) : 0ull;
-      const uint64_t le0 = cmp64<kCmpULE>(a0, t) & v0, le1 = cmp64<kCmpULE>(a1, t) & v1;
-      const uint64_t f0 = le0 & cmp64<kCmpUGE>(b0, tp), f1 = le1 & cmp64<kCmpUGE>(b1, tp);
-      const uint64_t l0 = ~le0 & v0 & cmp64<kCmpUGE>(b0 - a0, p), l1 = ~le1 & v1 & cmp64<kCmpUGE>(b1 - a1, p);
-      const bool fit = (f0 | f1) != 0;
-      const uint64_t m0 = fit ? f0 : l0, m1 = fit ? f1 : l1;
-      const int i = m0 ? (int)__builtin_ctzll(m0) : (m1 ? 64 + (int)__builtin_ctzll(m1) : -1);
-      if (i < 0) {
-        errs |= GG_DERR_STATE;
-      } else {
-        const uint32_t ui = (uint32_t)i;
-        const uint64_t a = A(ui), b = B(ui);
-        if (t >= a) {
-          if (t - a >= min_proc) {
-            if (b - (t + p) >= min_proc) { shift_up(ui + 1); set(ui + 1, t + p, b); ++sz; }
-            set(ui, a, t);
-          } else if (b - (t + p) >= min_proc) {
-            set(ui, t + p, b);
-          } else {
-            shift_down(ui); --sz;
-          }
-        } else {
-          qd = a - t;
-          if (b - (a + p) >= min_proc) set(ui, a + p, b);
-          else { shift_down(ui); --sz; }
-        }
-      }
-    }
-    sig_sq += p * p;                                                 // QueueModelMG1::updateQueue
-    sig += p;
+    sig_sq = rd64<RB>(sig_sq + p * p);                               // QueueModelMG1::updateQueue
+    sig = rd64<RB>(sig + p);
     if (sig_sq >= kMg1Exact || p >= (1ull << 26)) errs |= GG_DERR_RANGE;
-    ++nreq;
+    nreq = rd64<RB>(nreq + 1);
     const uint64_t x = t + qd + p;
-    newest = x > newest ? x : newest;
-    util += p;                                                       // updateQueueUtilizationCounters
-    last_req = x > last_req ? x : last_req;
-    ++total_req;
-    return qd;
+    newest = rd64<RB>(x > newest ? x : newest);
+    util = rd64<RB>(util + p);                                       // updateQueueUtilizationCounters
+    last_req = rd64<RB>(x > last_req ? x : last_req);
+    total_req = rd64<RB>(total_req + 1);
+    anl = rd64<RB>(anl);
   }
-  // The same request in halves, for a pipeline stage that forwards its packet
+  // The request in halves, for a pipeline stage that forwards its packet
   // as soon as the delay is known and does the bookkeeping while the next
   // stage runs (this queue's next request comes from the same wave, after
-  // it).  prune() is what every request does first; search() only reads the
-  // queue and gives the delay and the interval that serves [t, t+p]; apply()
-  // updates the interval list and the M/G/1 sums with that result.  Nothing
-  // touches the queue between the halves, so prune, search ... apply is the
-  // request made at the time of apply(): a wave that knows its next request
-  // ahead of the packet's arrival runs prune() and search() while it waits.
-  // One vector search serves every case (no last-interval pre-check: the
-  // walkers' requests land mid-list, and the last interval [x, inf) is found
+  // it).  prune() is what every request does first: a full list drops its
+  // oldest interval (the min node, :52-56), which in the ring is the head
+  // moving one position; search() only reads the queue and gives the delay
+  // and the (logical) interval that serves [t, t+p]; apply() updates the
+  // interval list and the M/G/1 sums with that result.  Nothing touches the
+  // queue between the halves, so prune, search ... apply is the request made
+  // at the time of apply(): a wave that knows its next request ahead of the
+  // packet's arrival runs prune() and search() while it waits.
+  // One vector search serves every case (the last interval [x, inf) is found
   // by the same compares): the interval holding t fits [t, t+p] -> no delay,
   // known after two compares; otherwise either the analytical branch
   // (interval 0 starts after t + p; never with a fit, whose interval starts at
-  // or before t) or the first later interval long enough.  Uniform values are
-  // kept scalar (readfirstlane) so a loop around it carries them in SGPRs.
-  __device__ __forceinline__ uint64_t rd64(uint64_t v) const { return rfl64(v); }
-  __device__ __forceinline__ uint64_t A1(uint32_t i) const { return i < 64 ? rl64(a0, i) : rl64(a1, i - 64); }
-  __device__ __forceinline__ uint64_t B1(uint32_t i) const { return i < 64 ? rl64(b0, i) : rl64(b1, i - 64); }
+  // or before t) or the first later interval long enough, which is the least
+  // logical index of its mask: the 128-bit mask rotated right by hd.
+  // A loop around the requests carries sz and hd through joins of branches
+  // on values loaded from memory, where the compiler holds them in VGPRs and
+  // would steer every use through exec masks: each half reads them back into
+  // SGPRs first (they are uniform).
+  __device__ __forceinline__ static uint32_t rd32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+  __device__ __forceinline__ void uni() { sz = rd32(sz); hd = rd32(hd); }
   enum : uint32_t { kFit = 0, kAnalytical = 1, kLater = 2, kNone = 3 };
   struct Found { uint64_t qd; uint32_t ui, kind; };
   __device__ __forceinline__ void prune()
   {
-    if (sz >= cap) { shift_down(0); --sz; }                          // prune the min node (:52-56)
+    uni();
+    const bool full = sz >= cap;
+    hd = full ? (hd + 1) & 127u : hd;
+    sz = full ? sz - 1 : sz;
   }
   __device__ __forceinline__ Found search(uint64_t t, uint64_t p) const
   {
     const uint64_t tp = t + p;
-    const uint64_t v0 = low_lanes(sz), v1 = sz > 64 ? low_lanes(sz - 64) : 0ull;
+    const uint32_t hd = rd32(this->hd), sz = rd32(this->sz);
+    const uint32_t l0 = (ln - hd) & 127u;
+    const uint64_t v0 = cmp32<kCmpULT>(l0, sz), v1 = cmp32<kCmpULT>(l0 ^ 64u, sz);   // the ring range [hd, hd + sz)
     const uint64_t le0 = cmp64<kCmpULE>(a0, t) & v0, le1 = cmp64<kCmpULE>(a1, t) & v1;
     const uint64_t f0 = le0 & cmp64<kCmpUGE>(b0, tp), f1 = le1 & cmp64<kCmpUGE>(b1, tp);
-    if (f0 | f1)                                                     // a <= t, t + p <= b: no delay
-      return Found{0ull, f0 ? (uint32_t)__builtin_ctzll(f0) : 64u + (uint32_t)__builtin_ctzll(f1), kFit};
-    if (analytical && (cmp64<kCmpUGT>(a0, tp) & 1ull))               // interval 0 starts after t + p
-      return Found{rd64(mg1_queue_delay(nreq, newest, sig_sq, sig)), 0u, kAnalytical};
+    if (f0 | f1) {                                                   // a <= t, t + p <= b: no delay (one lane at most)
+      const uint32_t x = f0 ? (uint32_t)__builtin_ctzll(f0) : 64u + (uint32_t)__builtin_ctzll(f1);
+      return Found{0ull, (x - hd) & 127u, kFit};
+    }
+    const uint32_t hs = hd & 63u;
+    if (analytical) {                                                // interval 0 (position hd) starts after t + p
+      const uint64_t g = hd < 64 ? cmp64<kCmpUGT>(a0, tp) : cmp64<kCmpUGT>(a1, tp);
+      if ((g >> hs) & 1ull) return Found{rfl64(mg1_queue_delay(nreq, newest, sig_sq, sig)), 0u, kAnalytical};
+    }
     const uint64_t m0 = ~le0 & v0 & cmp64<kCmpUGE>(b0 - a0, p);      // the first later interval long enough
     const uint64_t m1 = ~le1 & v1 & cmp64<kCmpUGE>(b1 - a1, p);
     if ((m0 | m1) == 0) return Found{0ull, 0u, kNone};
-    const uint32_t ui = m0 ? (uint32_t)__builtin_ctzll(m0) : 64u + (uint32_t)__builtin_ctzll(m1);
-    return Found{A1(ui) - t, ui, kLater};
+    const uint64_t x0 = hd < 64 ? m0 : m1, x1 = hd < 64 ? m1 : m0;   // bit i of (r1, r0): logical interval i
+    const uint64_t r0 = hs ? (x0 >> hs) | (x1 << (64u - hs)) : x0, r1 = hs ? (x1 >> hs) | (x0 << (64u - hs)) : x1;
+    const uint32_t ui = r0 ? (uint32_t)__builtin_ctzll(r0) : 64u + (uint32_t)__builtin_ctzll(r1);
+    return Found{A(ui) - t, ui, kLater};
   }
-  __device__ __forceinline__ void apply(uint64_t t, uint64_t p, const Found& s)
+  // The fit whose interval splits in two is three requests in four on a busy
+  // port: it runs from here to the updated list with no branch but the
+  // dispatch on kind.  Keeping the left part [a, t] and the right part
+  // [t+p, b] are scalar conditions.  One rotate (an empty mask unless both
+  // are kept) copies interval ui to ui + 1; then a part kept alone changes one
+  // bound of ui, and of two parts the left one is ui with end t, the right
+  // one ui + 1 with start t+p: two selects on the lanes' logical index, one
+  // writing starts and one ends.  A fit that keeps neither part erases the
+  // interval behind that.  RB: see account().
+  template <bool RB = false> __device__ __forceinline__ void apply(uint64_t t, uint64_t p, const Found& s)
   {
-    const uint64_t tp = t + p, qd = s.qd;
-    const uint32_t ui = s.ui;
-    if (s.kind == kFit) {
+    const uint64_t tp = t + p;
+    const uint32_t ui = rd32(s.ui), kind = rd32(s.kind);
+    uni();
+    if (kind == kFit) {
       ++n_gen;
-      const uint64_t a = A1(ui), b = B1(ui);
-      if (t - a >= min_proc) {
-        if (b - tp >= min_proc) { shift_up(ui + 1); set(ui + 1, tp, b); ++sz; }
-        set(ui, a, t);
-      } else if (b - tp >= min_proc) {
-        set(ui, tp, b);
-      } else {
-        shift_down(ui); --sz;
-      }
-    } else if (s.kind == kAnalytical) {
+      const uint32_t x = pos(ui);
+      const uint64_t ts = rfl64(t), tps = rfl64(tp);
+      const bool keepL = ts - PA(x) >= min_proc, keepR = PB(x) - tps >= min_proc, split = keepL && keepR;
+      const uint32_t l0 = li(), l1 = l0 ^ 64u;
+      const uint32_t k = split ? ui : 127u;
+      rotate_up(l0 > k, l1 > k);
+      const uint32_t sa = keepL ? 128u : ui, sa1 = split ? ui + 1 : 128u, sb = keepL ? ui : 128u;   // 128: no lane
+      a0 = (l0 == sa || l0 == sa1) ? tp : a0; a1 = (l1 == sa || l1 == sa1) ? tp : a1;
+      b0 = l0 == sb ? t : b0; b1 = l1 == sb ? t : b1;
+      sz += split ? 1u : 0u;
+      if (!keepL && !keepR) { shift_down(ui); --sz; }
+    } else if (kind == kAnalytical) {
       ++anl; ++n_anl;
-    } else if (s.kind == kNone) {
+    } else if (kind == kNone) {
       ++n_gen;
       errs |= GG_DERR_STATE;
     } else {
       ++n_gen;
-      const uint64_t a = A1(ui), b = B1(ui);
+      const uint64_t a = A(ui), b = B(ui);
       if (b - (a + p) >= min_proc) set(ui, a + p, b);
       else { shift_down(ui); --sz; }
     }
-    sig_sq = rd64(sig_sq + p * p);                                   // QueueModelMG1::updateQueue
-    sig = rd64(sig + p);
-    if (sig_sq >= kMg1Exact || p >= (1ull << 26)) errs |= GG_DERR_RANGE;
-    nreq = rd64(nreq + 1);
-    const uint64_t x = t + qd + p;
-    newest = rd64(x > newest ? x : newest);
-    util = rd64(util + p);                                           // updateQueueUtilizationCounters
-    last_req = rd64(x > last_req ? x : last_req);
-    total_req = rd64(total_req + 1);
-    anl = rd64(anl);
-    sz = (uint32_t)__builtin_amdgcn_readfirstlane((int)sz);
+    account<RB>(t, p, s.qd);
+  }
+  // computeQueueDelay (queue_model_history_tree.cc:44-126) + QueueModelMG1::updateQueue.
+  // The O(1) branch for a request served by the last interval stands in
+  // front of the general request, search() + apply().  TAIL: also the O(1)
+  // branch for requests served by the last two intervals (in-order streams:
+  // SELF / injection ports); the walkers' requests land mid-list 84 % of the
+  // time and skip that check (TAIL = false: search + apply serve those
+  // requests too, with the same result).
+  template <bool TAIL = true>
+  __device__ __forceinline__ uint64_t request(uint64_t t, uint64_t p, uint32_t* err)
+  {
+    errp = err;
+    prune();
+    {
+      const uint64_t la = A(sz - 1), lb = B(sz - 1);
+      if (la <= t && t + p <= lb && lb - (t + p) >= min_proc) {      // the last interval: no search, no delay
+        ++n_fast;
+        if (t - la >= min_proc) { set(sz - 1, la, t); set(sz, t + p, lb); ++sz; }
+        else set(sz - 1, t + p, lb);
+        account<true>(t, p, 0);
+        return 0;
+      }
+      if (TAIL && sz >= 2 && t < la && t >= A(sz - 2)) {
+        // the tail: interval sz-2 is the last one starting at or before t (and
+        // interval 0 starts before t: no M/G/1).  Either [t, t+p] fits in it, or
+        // the first later interval long enough is the last one (unbounded)
+        ++n_fast;
+        uint64_t qd = 0;
+        const uint32_t i2 = sz - 2, i1 = sz - 1;
+        const uint64_t a2 = A(i2), b2 = B(i2);
+        if (t + p <= b2) {
+          if (t - a2 >= min_proc) {
+            if (b2 - (t + p) >= min_proc) { set(i1 + 1, la, lb); set(i1, t + p, b2); ++sz; }
+            set(i2, a2, t);
+          } else if (b2 - (t + p) >= min_proc) {
+            set(i2, t + p, b2);
+          } else {
+            set(i2, la, lb); --sz;                                     // erase interval sz-2
+          }
+        } else {
+          qd = la - t;                                                 // queued behind the busy period
+          if (lb - (la + p) >= min_proc) set(i1, la + p, lb);
+          else --sz;                                                   // erase the last interval
+        }
+        account<true>(t, p, qd);
+        return qd;
+      }
+    }
+    const Found s = search(t, p);
+    apply<true>(t, p, s);
+    return s.qd;
   }
 };
 
