@@ -27,7 +27,7 @@ class GGError(RuntimeError):
     def __init__(self, code, msg, statuses=None):
         super().__init__("%s: %s" % (_ERR.get(code, code), msg))
         self.code = code
-        self.statuses = statuses     # coherent_run_many: the status of every instance
+        self.statuses = statuses     # coherent_run_many / coherent_advance_many: the status of every instance
 
 
 class LineInfo(ctypes.Structure):
@@ -65,7 +65,8 @@ EXPORTS = ["gg_abi_version", "gg_last_error", "gg_config_default", "gg_create", 
            "gg_stats_trace_configure", "gg_stats_trace_sample", "gg_stats_trace_get", "gg_stats_trace_dump",
            "gg_atac_params_default", "gg_noc_set_atac", "gg_atac_topology", "gg_noc_get_atac_counters",
            "gg_cache_track_miss_types", "gg_cache_get_miss_types",
-           "gg_coherent_advance", "gg_coherent_snapshot_size", "gg_coherent_snapshot", "gg_coherent_restore"]
+           "gg_coherent_advance", "gg_coherent_snapshot_size", "gg_coherent_snapshot", "gg_coherent_restore",
+           "gg_coherent_advance_many"]
 
 # statistics trace (gg_stats_trace_*): GG_ST_* statistics bits, GG_STF_* sample fields
 ST_NETWORK_UTILIZATION, ST_CACHE_LINE_REPLICATION = 1, 2
@@ -175,7 +176,10 @@ def load():
     L.gg_coherent_snapshot_size.argtypes = [vp, ctypes.POINTER(u64)]
     L.gg_coherent_snapshot.argtypes = [vp, vp, u64, ctypes.POINTER(u64)]
     L.gg_coherent_restore.argtypes = [vp, ctypes.POINTER(_Trace), vp, vp, u64, vp]
-    for name in ["gg_coherent_advance", "gg_coherent_snapshot_size", "gg_coherent_snapshot", "gg_coherent_restore"]:
+    L.gg_coherent_advance_many.argtypes = [ctypes.POINTER(vp), u32, ctypes.POINTER(u64), ctypes.POINTER(u64),
+                                           ctypes.POINTER(i32), ctypes.POINTER(i32), vp]
+    for name in ["gg_coherent_advance", "gg_coherent_snapshot_size", "gg_coherent_snapshot", "gg_coherent_restore",
+                 "gg_coherent_advance_many"]:
         getattr(L, name).restype = i32
     for name in ["gg_kernel_stats", "gg_shard_map", "gg_coherent_begin", "gg_coherent_quantum", "gg_coherent_export",
                  "gg_coherent_import", "gg_coherent_run", "gg_coherent_get_stats", "gg_gen_hotspot_trace",
@@ -645,6 +649,35 @@ def coherent_run_many(backends, addrs, metas, tile_offsets, outs=None, stream=No
     if rc != GG_OK:
         raise GGError(rc, load().gg_last_error().decode(errors="replace"), statuses)
     return statuses
+
+
+def coherent_advance_many(backends, stops=None, stream=None):
+    """An ensemble in legs (gg_coherent_advance_many): every backend has a
+    begun run (coherent_begin or coherent_restore); all of them are driven in
+    one set of launches until each is over or the quantum it would run next
+    is >= stops[i] (stops None, or an entry None: never).  Instances with a
+    statistics trace sample as a lone coherent_run does.  Returns the list of
+    (next_quantum, done) per instance, done 0 paused, 1 over.  If any
+    instance fails raises GGError carrying the per-instance statuses
+    (e.statuses) and that list (e.results) — the other instances have run to
+    their stop."""
+    n = len(backends)
+    if stops is not None and len(stops) != n:
+        raise ValueError("one stop per backend")
+    hs = (ctypes.c_void_p * max(n, 1))(*[be.h for be in backends])
+    sp = None
+    if stops is not None:
+        sp = (ctypes.c_uint64 * max(n, 1))(*[Backend.NEVER if q is None else int(q) for q in stops])
+    nq = (ctypes.c_uint64 * max(n, 1))()
+    dn = (ctypes.c_int * max(n, 1))()
+    st = (ctypes.c_int * max(n, 1))()
+    rc = load().gg_coherent_advance_many(hs, n, sp, nq, dn, st, _stream(stream))
+    results = [(int(nq[i]), int(dn[i])) for i in range(n)]
+    if rc != GG_OK:
+        e = GGError(rc, load().gg_last_error().decode(errors="replace"), [int(st[i]) for i in range(n)])
+        e.results = results
+        raise e
+    return results
 
 
 def shard_map(num_tiles, num_shards):

@@ -8,6 +8,7 @@
 // leave QS_START = slot + 1), so a sample costs no host round trip and the
 // step and walker kernels are untouched.
 #include "gg_stats.h"
+#include "gg_coh_many.h"
 
 #include <cstring>
 #include <sstream>
@@ -71,12 +72,16 @@ __device__ __forceinline__ void count_entries(const GG_DP DEnt* d, uint32_t n, u
 // of the device-driven loop (a sample only if the slot ended a quantum and a
 // multiple of the interval lies among the barrier times it passes); else one
 // sample at that time.  The sample's words are zero beforehand (gg_stats_begin).
-__global__ void __launch_bounds__(256) k_stats_scan(CP P, CS S, StatsDev D, uint32_t L, uint64_t barrier_ns)
+// The body of k_stats_scan and k_stats_scan_many (as step_body / walk_body,
+// gg_coh_many.h): gridDim.x is the instance's own tile count in both.
+// nt = blockDim.x, read by the kernel itself (only there is it the launch's one word).
+__device__ __forceinline__ void stats_scan_body(const CP& P, const CS& S, const StatsDev& D, uint32_t L, uint64_t barrier_ns,
+                                                uint32_t nt)
 {
   extern __shared__ uint32_t hist[];     // [T + 1] (cache_line_replication)
   __shared__ uint32_t cnt[4];            // L1 exclusive, L1 shared, L2 exclusive, L2 shared
   __shared__ unsigned long long fl[3];   // flits sent, broadcast, received of this workgroup's share of the tiles
-  const uint32_t tid = threadIdx.x, nt = blockDim.x, lt = blockIdx.x;
+  const uint32_t tid = threadIdx.x, lt = blockIdx.x;
   uint64_t time_ns = barrier_ns, repeat = 1;
   if (barrier_ns == kSlotTime) {
     if (S.qs[QS_START] != (uint64_t)L + 1) return;         // no quantum ended in this slot
@@ -152,6 +157,33 @@ __global__ void __launch_bounds__(256) k_stats_scan(CP P, CS S, StatsDev D, uint
   D.hdr[SH_ARRIVED] = 0;
   __hip_atomic_store(&D.hdr[SH_COUNT], idx + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   __threadfence();
+}
+
+__global__ void __launch_bounds__(256) k_stats_scan(CP P, CS S, StatsDev D, uint32_t L, uint64_t barrier_ns)
+{
+  stats_scan_body(P, S, D, L, barrier_ns, blockDim.x);
+}
+
+// The scan of slot L for the live instances of an ensemble
+// (gg_coherent_advance_many), grid (owned tiles, live instances): devs[j] is
+// the trace of the instance at pairs[j], statistics = 0 for one without.  A
+// slot ends a quantum with a sample due about once in a thousand, so what
+// counts is the way out: the instance's words are wave-uniform and constant
+// for the launch (the host writes them with the live list), read through the
+// constant address space as the other ensemble kernels read P and S, and the
+// quantum state is written by earlier launches only — scalar loads up to the
+// return, two in a row (the record carries CS::qs, so the way to QS_START
+// does not lead through the pair and the instance's CS).
+struct StatsMany { StatsDev D; const uint64_t* qs; };
+__global__ void __launch_bounds__(256) k_stats_scan_many(const ManyPair* __restrict__ pairs,
+                                                         const StatsMany* __restrict__ devs, uint32_t L)
+{
+  const StatsMany& E = *launch_const(devs + blockIdx.y);
+  if (E.D.statistics == 0) return;
+  typedef const uint64_t __attribute__((address_space(4))) * CQ;
+  if (((CQ)(uintptr_t)E.qs)[QS_START] != (uint64_t)L + 1) return;   // (the body's own test, on the scalar path)
+  const ManyPair pr = *launch_const(pairs + blockIdx.y);
+  stats_scan_body(*launch_const(pr.P), *launch_const(pr.S), E.D, L, kSlotTime, blockDim.x);
 }
 
 }  // namespace ggc
@@ -240,6 +272,22 @@ gg_status gg_stats_slot(gg_ctx* ctx, hipStream_t s, uint32_t L)
 {
   if (!ctx->stats || !ctx->stats->D.statistics) return GG_OK;
   return stats_launch(ctx, s, L, kSlotTime);     // (a launch failure: the batch's hipGetLastError)
+}
+
+// ---- the ensemble (gg_coherent_advance_many): one record per live instance,
+// rebuilt with the live list, and one scan launch per slot for all of them
+uint32_t gg_stats_run_bits(const gg_ctx* ctx) { return ctx->stats ? ctx->stats->D.statistics : 0; }
+size_t gg_stats_many_bytes() { return sizeof(StatsMany); }
+void gg_stats_many_fill(gg_ctx* ctx, const CS& S, void* rec)
+{
+  StatsMany e{};
+  if (gg_stats_run_bits(ctx)) { e.D = ctx->stats->D; e.qs = (const uint64_t*)S.qs; }
+  std::memcpy(rec, &e, sizeof(e));
+}
+void gg_stats_many_slot(const ManyPair* pairs, const void* recs, uint32_t tiles, uint32_t live, size_t lds, hipStream_t s,
+                        uint32_t L)
+{
+  hipLaunchKernelGGL(k_stats_scan_many, dim3(tiles, live), dim3(256), lds, s, pairs, (const StatsMany*)recs, L);
 }
 
 static gg_status stats_active(gg_ctx* ctx, const char* what)

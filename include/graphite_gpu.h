@@ -575,10 +575,60 @@ gg_status gg_coherent_run(gg_ctx* ctx, const gg_trace* trace, uint64_t* access_o
  * there hangs the device.  The per-step launches give bit-identical results
  * (gg_coherent_run has both forms).  Launches are not timed per kernel; the
  * "coherent_run" timer of gg_set_timing covers the whole call on ctxs[0].
- * One stream, one host thread; synchronous.                                 */
+ * One stream, one host thread; synchronous.
+ * A context with a statistics trace configured is refused
+ * (GG_ERR_UNSUPPORTED, naming the index).  A traced sweep is
+ * gg_coherent_begin per context, then gg_coherent_advance_many (below),
+ * which samples.                                                            */
 #define GG_MANY_MAX 4096u
 gg_status gg_coherent_run_many(gg_ctx* const* ctxs, uint32_t n, const gg_trace* traces,
                                uint64_t* const* access_out_dev, gg_status* statuses, void* stream);
+/* An ensemble in legs, and with statistics traces: gg_coherent_advance_many
+ * is to gg_coherent_run_many what gg_coherent_advance (below) is to
+ * gg_coherent_run.  Every context has a begun run driven by the device loop
+ * (gg_coherent_begin or gg_coherent_restore); the call drives all of them in
+ * one set of launches on stream.  Instance i stops when its run is over or
+ * when the quantum the device picked next is >= stop_quanta[i] (stop_quanta
+ * NULL: ~0, never, for all).  next_quanta[i] and dones[i] (0 paused, 1 over,
+ * 2 deadlock) receive what gg_coherent_advance(ctxs[i], stop_quanta[i], ...)
+ * would return, statuses[i] (may be NULL) its status; for one instance the
+ * call is indistinguishable from that one, whatever company it has:
+ *  - An instance that is already over, or whose stop is <= its current next
+ *    quantum, gets no launch and no change of state, reports its current
+ *    (next, done) and never enters the launches.
+ *  - Every other instance is resumed as gg_coherent_advance resumes it (the
+ *    stop stored, the launch index restarted at 0 — for all of them together
+ *    — a pending BARRIER release kept) and runs in the per-step launches, the
+ *    only form an ensemble has, under every stop value.  Instances that
+ *    finish, pause or fail leave the launches at the next batch boundary.
+ *  - A device capacity error gives GG_ERR_UNSUPPORTED, a deadlock
+ *    GG_ERR_STATE, a full sample buffer GG_ERR_UNSUPPORTED ("sample buffer");
+ *    a failed instance ends alone, the others run on.  The return value is
+ *    the first non-zero status, or GG_OK.
+ *  - Each context's own last stream is synchronised before the first launch;
+ *    afterwards the getters of a driven context wait on stream.
+ * Statistics traces.  A context whose begun run has a trace
+ * (gg_stats_trace_configure before gg_coherent_begin) is accepted.  The
+ * launches of a slot are followed by one scan launch for all live instances
+ * (k_stats_scan_many, grid (tiles, live instances)) while at least one of
+ * them has a trace, none otherwise.  Traced and untraced instances, different
+ * statistics bits, intervals and max_samples go together; each instance's
+ * samples are those of a lone gg_coherent_run, bit for bit, and a full buffer
+ * fails that instance only.  A sample due at a pause boundary is taken with
+ * its real time_ns and repeat (section 4i's rule).
+ * Snapshots stay per context: gg_coherent_snapshot on a paused instance gives
+ * the bytes a lone context paused at the same quantum gives.
+ * Rejections, all before any launch or any write to any context's state, each
+ * naming the context index.  GG_ERR_INVALID: n == 0, n > GG_MANY_MAX, NULL
+ * ctxs / next_quanta / dones, a NULL or repeated context, a context with no
+ * begun run or one driven by gg_coherent_quantum / the round, a set that is
+ * not launch-compatible (gg_coherent_run_many's rule, naming the field).
+ * GG_ERR_UNSUPPORTED: a context that does not own every shard, an ATAC
+ * context ("batch API only").
+ * Not in scope: a multi-rank sweep, a snapshot holding several instances.
+ * One stream, one host thread; synchronous.                                 */
+gg_status gg_coherent_advance_many(gg_ctx* const* ctxs, uint32_t n, const uint64_t* stop_quanta,
+                                   uint64_t* next_quanta, int* dones, gg_status* statuses, void* stream);
 /* A coherent run in legs: pause at a quantum boundary, snapshot, restore
  * (DESIGN.md section 4i).
  * gg_coherent_advance runs the device-driven loop of gg_coherent_run from the
@@ -622,9 +672,11 @@ gg_status gg_coherent_run_many(gg_ctx* const* ctxs, uint32_t n, const gg_trace* 
  * for a different config, launch state or tile_offsets, a truncated or
  * corrupted buffer, a section past the buffer or of another size than the
  * context's own.
- * Not in scope: gg_coherent_run_many, the multi-rank round, a context that
- * does not own every shard (GG_ERR_UNSUPPORTED), changing any setting
- * across a restore.                                                         */
+ * An ensemble in legs: gg_coherent_advance_many (above) pauses and resumes
+ * many begun runs in one set of launches; snapshot and restore stay per
+ * context.
+ * Not in scope: the multi-rank round, a context that does not own every
+ * shard (GG_ERR_UNSUPPORTED), changing any setting across a restore.        */
 gg_status gg_coherent_advance(gg_ctx* ctx, uint64_t stop_quantum, uint64_t* next_quantum, int* done);
 gg_status gg_coherent_snapshot_size(gg_ctx* ctx, uint64_t* bytes);
 gg_status gg_coherent_snapshot(gg_ctx* ctx, void* host_buf, uint64_t cap, uint64_t* bytes);
@@ -774,7 +826,9 @@ gg_status gg_dump_summary(gg_ctx* ctx, int format, char* buf, uint64_t cap, uint
  * launches, the same kernels.  gg_coherent_run_many and gg_coherent_run_ranks
  * return GG_ERR_UNSUPPORTED for a context with a trace configured (the counts
  * are additive over contexts: a rank samples its own shards with
- * gg_stats_trace_sample).
+ * gg_stats_trace_sample).  An ensemble of traced runs is gg_coherent_begin
+ * per context, then gg_coherent_advance_many: one scan launch per slot for
+ * all its live instances.
  * gg_stats_trace_sample appends one sample (repeat 1) of the context's
  * current state at barrier_time_ns: between the quanta of a host-driven run
  * (gg_coherent_quantum), or after a finished gg_coherent_run for the
