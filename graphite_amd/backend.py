@@ -66,7 +66,8 @@ EXPORTS = ["gg_abi_version", "gg_last_error", "gg_config_default", "gg_create", 
            "gg_atac_params_default", "gg_noc_set_atac", "gg_atac_topology", "gg_noc_get_atac_counters",
            "gg_cache_track_miss_types", "gg_cache_get_miss_types",
            "gg_coherent_advance", "gg_coherent_snapshot_size", "gg_coherent_snapshot", "gg_coherent_restore",
-           "gg_coherent_advance_many"]
+           "gg_coherent_advance_many",
+           "gg_coherent_begin_window", "gg_coherent_next_window", "gg_coherent_window_state"]
 
 # statistics trace (gg_stats_trace_*): GG_ST_* statistics bits, GG_STF_* sample fields
 ST_NETWORK_UTILIZATION, ST_CACHE_LINE_REPLICATION = 1, 2
@@ -180,6 +181,11 @@ def load():
                                            ctypes.POINTER(i32), ctypes.POINTER(i32), vp]
     for name in ["gg_coherent_advance", "gg_coherent_snapshot_size", "gg_coherent_snapshot", "gg_coherent_restore",
                  "gg_coherent_advance_many"]:
+        getattr(L, name).restype = i32
+    L.gg_coherent_begin_window.argtypes = [vp, ctypes.POINTER(_Trace), vp, vp, vp]
+    L.gg_coherent_next_window.argtypes = [vp, ctypes.POINTER(_Trace), vp, vp, vp]
+    L.gg_coherent_window_state.argtypes = [vp, vp, vp]
+    for name in ["gg_coherent_begin_window", "gg_coherent_next_window", "gg_coherent_window_state"]:
         getattr(L, name).restype = i32
     for name in ["gg_kernel_stats", "gg_shard_map", "gg_coherent_begin", "gg_coherent_quantum", "gg_coherent_export",
                  "gg_coherent_import", "gg_coherent_run", "gg_coherent_get_stats", "gg_gen_hotspot_trace",
@@ -411,7 +417,8 @@ class Backend:
         """The device-driven loop from the current state (after coherent_begin
         or coherent_restore) until the run is over or the next quantum is >=
         stop_quantum.  Returns (next_quantum, done): done 0 paused, 1 over
-        (a deadlock raises, as coherent_run does)."""
+        (a deadlock raises, as coherent_run does), NEED_WINDOW on a windowed
+        run whose next quantum needs the next windows (coherent_next_window)."""
         nq, done = ctypes.c_uint64(0), ctypes.c_int(0)
         _check(load().gg_coherent_advance(self.h, stop_quantum, ctypes.byref(nq), ctypes.byref(done)))
         return nq.value, done.value
@@ -447,6 +454,47 @@ class Backend:
         tr = self._trace(addr, meta, tile_offsets)
         _check(load().gg_coherent_restore(self.h, ctypes.byref(tr), _ptr(out), b.ctypes.data_as(ctypes.c_void_p),
                                           b.size, _stream(stream)))
+
+    # ---- a run fed its trace in windows (gg_coherent_begin_window / _next_window / _window_state)
+    NEED_WINDOW = 3                     # GG_ADV_NEED_WINDOW: coherent_advance's done on a windowed run
+
+    def _window(self, fn, addr, meta, tile_offsets, out, final_tiles, stream):
+        import torch
+        if out is not None:
+            _need_dev(out, torch.int64, addr.numel())
+        fin = None
+        if final_tiles is not None:
+            fin = np.ascontiguousarray(final_tiles, dtype=np.uint8)
+            if fin.size != self.cfg.num_tiles:
+                raise ValueError("final_tiles needs num_tiles entries")
+        tr = self._trace(addr, meta, tile_offsets)
+        _check(fn(self.h, ctypes.byref(tr), _ptr(out), None if fin is None else fin.ctypes.data_as(ctypes.c_void_p),
+                  _stream(stream)))
+
+    def coherent_begin_window(self, addr, meta, tile_offsets, out=None, final_tiles=None, stream=None):
+        """coherent_begin with a first window of every tile's records
+        (tile_offsets index the window's own arrays).  final_tiles[t] != 0:
+        tile t's window runs to the end of its trace.  The run is driven by
+        coherent_advance, which returns done == NEED_WINDOW when the next
+        windows are due."""
+        self._window(load().gg_coherent_begin_window, addr, meta, tile_offsets, out, final_tiles, stream)
+
+    def coherent_next_window(self, addr, meta, tile_offsets, out=None, final_tiles=None, stream=None):
+        """The next windows of a paused (or not yet advanced) windowed run:
+        tile t's records begin at its first unconsumed record
+        (coherent_window_state's consumed[t]).  After the call the previous
+        arrays are the caller's again."""
+        self._window(load().gg_coherent_next_window, addr, meta, tile_offsets, out, final_tiles, stream)
+
+    def coherent_window_state(self):
+        """(consumed, min_records), uint64 [num_tiles] each: the records every
+        tile has consumed since begin, and what its next window must hold (up
+        to its last record that is no CONT line and no BARRIER) for the next
+        quantum to run; 0 for final and finished tiles."""
+        T = self.cfg.num_tiles
+        c, m = np.zeros(T, np.uint64), np.zeros(T, np.uint64)
+        _check(load().gg_coherent_window_state(self.h, c.ctypes.data_as(ctypes.c_void_p), m.ctypes.data_as(ctypes.c_void_p)))
+        return c, m
 
     def round_pack(self, world, rank, q):
         """gg_round_pack: quantum q's steps + the tail on the context's stream;

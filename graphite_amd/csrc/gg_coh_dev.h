@@ -144,6 +144,20 @@ enum { QS_Q = 0, QS_START, QS_DONE, QS_ARRIVED, QS_ACTIVE, QS_BLOCKED, QS_MIN_NE
 // batch return as after a finished run, and the rest of the quantum state
 // says where the run continues (the host clears the word to resume)
 constexpr uint64_t kQsPaused = 4;
+// a windowed run (gg_coherent_begin_window): the quantum picked
+// to run next is not safe for some tile whose window does not reach the end
+// of its trace; a pause like kQsPaused (no bit of "over": QS_DONE & 3 == 0)
+constexpr uint64_t kQsWindow = 8;
+// CS::win of a windowed run: two words of the run, then WN_TILE words per
+// owned tile.  WN_ACC gathers the least horizon of a quantum end (qend_tile),
+// WN_HOR keeps the last one gathered (qend_pick, the hand-over kernel): the
+// latest barrier time of a quantum in which no tile can consume the last
+// record of its window.
+enum { WN_ACC = 0, WN_HOR, WN_HDR = 2 };
+// per tile: the last record of the window that is neither a GG_META_CONT line
+// nor a BARRIER record (the guard; ~0 for a final tile), the final flag, the
+// records consumed before the window, the window's first record
+enum { WN_GUARD = 0, WN_FINAL, WN_CBASE, WN_FIRST, WN_TILE };
 constexpr uint32_t kBarWait = 2;          // Tile::blocked of a tile waiting at a BARRIER record
 // gap cycles before a record (a BARRIER record is taken at the tile's clock)
 __device__ __forceinline__ uint64_t rec_gap(uint32_t meta)
@@ -223,6 +237,7 @@ struct CS {
   GG_DP uint32_t* imp;                         // [2] held packets imported for the quantum of parity Q & 1
   GG_DP uint32_t* live;                        // [4] launch L & 3: step index + 1 of a step launch, 0 otherwise
   GG_DP uint64_t* qs;                          // device-driven run: QS_* below
+  GG_DP uint64_t* win;                         // a windowed run's WN_* words; null otherwise
   GG_DP uint64_t* ri; GG_DP uint32_t* err;
   GG_DP HQueue* nq; GG_DP HNode* nnd;                // router queues [tile * 6 + port]
   GG_DP uint64_t* ctr;                         // NoC counters [T][GG_NUM_NET_COUNTERS]
@@ -2685,9 +2700,37 @@ __device__ __forceinline__ void import_one(const CP& P, const CS& S, const gg_cm
 // to arrive picks the next quantum as gg_coherent_run / oracle_coh_run do
 // (empty quanta skipped; blocked tiles with nothing in flight = deadlock).
 
+// A windowed run: the tile's horizon, the latest barrier time of a quantum in
+// which it provably cannot consume the last record of its window (DESIGN.md
+// §4j).  To get there it must start the guard g, a record that starts only
+// before the barrier; each of the g - rec records before g moves the clock on
+// by at least the L1-D hit path (P.lat_l1d; a pending miss completes later
+// still), but for the one BARRIER record a quantum can release.
+__device__ __forceinline__ uint64_t win_horizon(const CP& P, uint64_t rec, uint64_t clk, uint64_t guard)
+{
+  return guard > rec ? clk + (guard - rec - 1) * P.lat_l1d : 0ull;
+}
+// The backstop: a tile off the end of a window that is not the end of its
+// trace is no finished tile.  The run fails (GG_DERR_WINDOW), and the tile
+// counts as blocked so that no quantum end can call the run over.
+__device__ __forceinline__ void qend_window(const CP& P, const CS& S, uint32_t lt)
+{
+  const GG_DP uint64_t* w = S.win + WN_HDR + (size_t)lt * WN_TILE;
+  if (w[WN_FINAL]) return;
+  const uint64_t r = S.ts[lt].rec;
+  uint64_t h = 0;
+  if (r >= S.ts[lt].rec_end) {
+    atomicOr(S.err, GG_DERR_WINDOW);
+    atomicAdd((unsigned long long*)&S.qs[QS_ACTIVE], 1ull);
+    atomicAdd((unsigned long long*)&S.qs[QS_BLOCKED], 1ull);
+  } else h = win_horizon(P, r, S.ts[lt].clk, w[WN_GUARD]);
+  atomicMin((unsigned long long*)&S.win[WN_ACC], (unsigned long long)h);
+}
+
 // one owned tile's status into the quantum state
 __device__ __forceinline__ void qend_tile(const CP& P, const CS& S, uint32_t lt)
 {
+  if (S.win) qend_window(P, S, lt);
   const uint64_t r = S.ts[lt].rec;
   if (r < S.ts[lt].rec_end) {
     atomicAdd((unsigned long long*)&S.qs[QS_ACTIVE], 1ull);
@@ -2766,7 +2809,16 @@ __device__ __forceinline__ void qend_pick(const CS& S, uint32_t L, uint64_t q, u
   qs[QS_Q] = nq; qs[QS_START] = L + 1; qs[QS_COUNT] = Q + 1;
   // the pause of gg_coherent_advance: once per quantum, here, where the state
   // is whole (held records imported, ring zeroed, release stored)
-  if (!done && nq >= qs[QS_STOP]) done = kQsPaused;
+  // a windowed run pauses the same way before a quantum whose barrier is past
+  // the least horizon the tiles gathered (gg_coherent_advance's stop first:
+  // the next advance then asks for the windows with no launch)
+  if (S.win) {
+    volatile uint64_t* w = S.win;
+    const uint64_t h = w[WN_ACC];
+    w[WN_HOR] = h; w[WN_ACC] = ~0ull;
+    if (!done && (nq + 1) * qps > h) done = kQsWindow;
+  }
+  if ((!done || done == kQsWindow) && nq >= qs[QS_STOP]) done = kQsPaused;
   qs[QS_DONE] = done;
   __threadfence();
 }
@@ -3528,6 +3580,10 @@ __device__ __forceinline__ uint64_t tile_step(const CP& P, const CS& S, uint32_t
     for (int i = 0; i < 9; ++i) r[23 + i] = T.tra[i];
   }
   // the tile's next start for the shard scheduler: finished, blocked, or clock + gap
+  // (kNsFin does not tell a finished tile from one at the end of a window
+  // that is not the end of its trace: only k_c_persist's scheduler reads it,
+  // and coh_drive keeps a windowed run off the persistent kernels; the
+  // quantum end tells the two apart, qend_window)
   if (T.rec >= T.rec_end) return kNsFin;
   if (T.blocked) return kNsBlk;
   return T.clk + rec_gap(S.meta[T.rec]) * P.gap_ps;

@@ -5,6 +5,7 @@
 #include "gg_coh_many.h"
 #include "gg_stats.h"
 #include "gg_snapshot.h"
+#include "gg_coh_window.h"
 
 #include <algorithm>
 #include <cmath>
@@ -251,6 +252,15 @@ struct gg_coh_state {
   bool begun = false;
   uint64_t gen = 0;                     // gg_coherent_begin count: a round in progress belongs to one run
   bool has_barrier = false;             // the bound trace holds BARRIER records (not for gg_coherent_quantum)
+  // a windowed run (gg_coherent_begin_window): S.win's array,
+  // a window's final flags on the device (its tile offsets go through
+  // offs_dev), the hand-over kernel's verdict, the window-state kernel's
+  // output [2][T]
+  bool windowed = false;
+  uint64_t* win_dev = nullptr;
+  uint8_t* win_fin_dev = nullptr;
+  uint32_t* win_bad_dev = nullptr;
+  uint64_t* win_state_dev = nullptr;
   // who drives the begun run: nobody yet, the device loop (gg_coherent_run /
   // _advance) or the host (gg_coherent_quantum, the round) — they keep
   // different state words, so one run takes one of them
@@ -718,6 +728,13 @@ static gg_status coh_alloc(gg_ctx* ctx)
   return GG_OK;
 }
 
+// the backstop of a windowed run (qend_window): the safe-quantum rule let a
+// tile run off a window that is not the end of its trace
+static gg_status coh_window_exhausted()
+{
+  return gg_fail(GG_ERR_STATE, "coherent mode: window exhausted (a tile reached the end of a window that is not the "
+                               "end of its trace; the run's results are void)");
+}
 static gg_status coh_check(gg_ctx* ctx)
 {
   uint32_t ew[2] = {0, 0};
@@ -732,6 +749,7 @@ static gg_status coh_check(gg_ctx* ctx)
                                           "there are tiles (the scan of gg_stats.hip)");
   if (e & GG_DERR_SAMPLES) return gg_fail(GG_ERR_UNSUPPORTED, "statistics trace: the sample buffer is full "
                                           "(max_samples of gg_stats_trace_configure); no sample was dropped silently");
+  if (e & GG_DERR_WINDOW) return coh_window_exhausted();
   return GG_OK;
 }
 
@@ -758,6 +776,7 @@ gg_status gg_coherent_begin(gg_ctx* ctx, const gg_trace* tr, uint64_t* access_ou
     if (tr->tile_offsets[t] > tr->tile_offsets[t + 1]) return gg_fail(GG_ERR_INVALID, "tile_offsets not monotone");
   if (tr->num_records && (!tr->addr_dev || !tr->meta_dev)) return gg_fail(GG_ERR_INVALID, "NULL trace pointers");
   cs_set(C->S.addr, tr->addr_dev); cs_set(C->S.meta, tr->meta_dev); cs_set(C->S.out, access_out_dev);
+  C->S.win = nullptr; C->windowed = false;           // (gg_coherent_begin_window sets them after this begin)
   GG_HIP(hipMemcpyAsync(C->Pd, &C->P, sizeof(CP), hipMemcpyHostToDevice, s));
   GG_HIP(hipMemcpyAsync(C->Sd, &C->S, sizeof(CS), hipMemcpyHostToDevice, s));
   C->n_records = tr->num_records;
@@ -954,6 +973,7 @@ gg_status gg_coh_import_slots(gg_ctx* ctx, const gg_cmsg* slots, uint32_t world,
 
 gg_status gg_coh_check(gg_ctx* ctx) { return coh_check(ctx); }
 uint64_t gg_coh_generation(gg_ctx* ctx) { return ctx->coh ? ctx->coh->gen : 0; }
+bool gg_coh_windowed(const gg_ctx* ctx) { return ctx && ctx->coh && ctx->coh->begun && ctx->coh->windowed; }
 
 gg_status gg_coherent_export(gg_ctx* ctx, gg_cmsg* out_dev, uint64_t cap, uint64_t* per_shard_counts)
 {
@@ -1031,6 +1051,10 @@ static gg_status coh_drive(gg_ctx* ctx, bool may_persist, uint64_t* done_out)
   const char* nl_env = getenv("GG_COH_NO_LDS_CACHE");
   const bool plc = C->persist_lc && !(nl_env && atoi(nl_env));
   bool persist = may_persist && P.L <= kPersistTiles && !P.mosi && !P.shl2 && !(np_env && atoi(np_env));   // (no persistent MOSI / sh_l2 instance)
+  // a windowed run: never (k_c_persist keeps a TraceWin across steps, has no
+  // clean point for a hand-over, and its scheduler reads next_start's kNsFin,
+  // which takes a tile at the end of a window for a finished one)
+  if (C->windowed) persist = false;
   // a statistics trace: one more launch per slot, the scan, which returns at
   // once unless the slot ended a quantum with a sample due (gg_stats.hip); the
   // per-step launches on every mesh size (a persistent launch holds cache
@@ -1203,7 +1227,26 @@ gg_status gg_coherent_advance(gg_ctx* ctx, uint64_t stop_quantum, uint64_t* next
   *next_quantum = qs[QS_Q];
   *done = (int)(qs[QS_DONE] & 3);
   if (*done == 2) return gg_fail(GG_ERR_STATE, "coherent run deadlocked: tiles blocked with no message in flight");
+  if (C->windowed) {
+    // test knob: GG_WINDOW_FAIL_EXHAUSTED=1 sets the backstop's error bit on
+    // the host, as qend_window does for a tile off a window that is not the
+    // end of its trace (no tile is driven there); the run fails from here on
+    const char* e = getenv("GG_WINDOW_FAIL_EXHAUSTED");
+    if (e && atoi(e)) {
+      uint32_t ew = 0;
+      GG_HIP(hipMemcpy(&ew, ctx->err_dev, sizeof(ew), hipMemcpyDeviceToHost));
+      ew |= GG_DERR_WINDOW;
+      GG_HIP(hipMemcpy(ctx->err_dev, &ew, sizeof(ew), hipMemcpyHostToDevice));
+    }
+  }
   if (*done || stop_quantum <= qs[QS_Q]) return coh_check(ctx);   // over, or already there: no launch, no change
+  if (C->windowed) {
+    // the quantum to run next against the horizon the last quantum end or
+    // hand-over left: windows already too short ask for the next ones at once
+    uint64_t hor = 0;
+    GG_HIP(hipMemcpy(&hor, C->win_dev + WN_HOR, sizeof(hor), hipMemcpyDeviceToHost));
+    if ((qs[QS_Q] + 1) * qs[QS_QPS] > hor) { *done = GG_ADV_NEED_WINDOW; return coh_check(ctx); }
+  }
   // resume: the launch index restarts at 0, so the quantum's step 0 is launch
   // 0 (k = L - QS_START) and no slot of the live ring is a step; the rest of
   // the quantum state, QS_REL (a barrier release for step 0) included, stays
@@ -1212,11 +1255,141 @@ gg_status gg_coherent_advance(gg_ctx* ctx, uint64_t stop_quantum, uint64_t* next
   GG_HIP(hipMemsetAsync(C->S.live, 0, 4 * sizeof(uint32_t), s));
   GG_HIP(hipStreamSynchronize(s));                     // (qs is a stack array)
   uint64_t d = 0;
-  const gg_status st = coh_drive(ctx, stop_quantum == ~0ull, &d);
-  *done = (int)(d & 3);
+  const gg_status st = coh_drive(ctx, stop_quantum == ~0ull && !C->windowed, &d);   // (k_c_persist keeps a TraceWin across steps)
+  *done = d == kQsWindow ? GG_ADV_NEED_WINDOW : (int)(d & 3);
+  if (C->windowed && st != GG_OK && *done == 1) *done = 0;   // a failed windowed run is never reported over
   uint64_t q = 0;
   if (hipMemcpy(&q, C->S.qs + QS_Q, sizeof(q), hipMemcpyDeviceToHost) == hipSuccess) *next_quantum = q;
   return st;
+}
+
+// ---- a run fed its trace in windows -------------------------
+// a window's offsets and final flags onto the device; the host-side checks
+// both entries share
+static gg_status win_upload(gg_ctx* ctx, const char* what, const gg_trace* win, const uint8_t* final_tiles, hipStream_t s)
+{
+  gg_coh_state* C = ctx->coh;
+  const uint32_t T = C->P.T;
+  if (win->tile_offsets[T] != win->num_records) return gg_fail(GG_ERR_INVALID, "%s: tile_offsets[num_tiles] != num_records", what);
+  for (uint32_t t = 0; t < T; ++t)
+    if (win->tile_offsets[t] > win->tile_offsets[t + 1]) return gg_fail(GG_ERR_INVALID, "%s: tile_offsets not monotone", what);
+  if (win->num_records && (!win->addr_dev || !win->meta_dev)) return gg_fail(GG_ERR_INVALID, "%s: NULL trace pointers", what);
+  if (!C->win_dev) {
+    if (gg_status st = C->mem.alloc(&C->win_dev, (uint64_t)WN_HDR + (uint64_t)C->P.L * WN_TILE)) return st;
+    if (gg_status st = C->mem.alloc(&C->win_fin_dev, (uint64_t)T)) return st;
+    if (gg_status st = C->mem.alloc(&C->win_bad_dev, 2)) return st;
+    if (gg_status st = C->mem.alloc(&C->win_state_dev, 2 * (uint64_t)T)) return st;
+  }
+  // (offs_dev is read by k_c_reset at begin only: between begins it stages a window's offsets)
+  GG_HIP(hipMemcpyAsync(C->offs_dev, win->tile_offsets, sizeof(uint64_t) * (T + 1), hipMemcpyHostToDevice, s));
+  if (final_tiles) GG_HIP(hipMemcpyAsync(C->win_fin_dev, final_tiles, T, hipMemcpyHostToDevice, s));
+  else GG_HIP(hipMemsetAsync(C->win_fin_dev, 0, T, s));
+  const uint32_t bad0[2] = {0u, ~0u};
+  GG_HIP(hipMemcpyAsync(C->win_bad_dev, bad0, sizeof(bad0), hipMemcpyHostToDevice, s));
+  GG_HIP(hipStreamSynchronize(s));                     // (the sources are the caller's and a stack array)
+  return GG_OK;
+}
+
+gg_status gg_coherent_begin_window(gg_ctx* ctx, const gg_trace* win, uint64_t* access_out_dev, const uint8_t* final_tiles,
+                                   void* stream)
+{
+  const char* const what = "gg_coherent_begin_window";
+  GG_NOT_ATAC(ctx, what);
+  if (!ctx || !win || !win->tile_offsets) return gg_fail(GG_ERR_INVALID, "%s: NULL argument", what);
+  if (gg_status st = coh_owns_all(ctx, GG_ERR_UNSUPPORTED, what)) return st;
+  hipSetDevice(ctx->device);
+  if (gg_status st = coh_alloc(ctx)) return st;
+  gg_coh_state* C = ctx->coh;
+  if (C->P.lat_l1d == 0)
+    return gg_fail(GG_ERR_UNSUPPORTED, "%s: with zero L1-D data cycles a record can cost no time, so no window "
+                                       "bounds what a tile consumes in a quantum", what);
+  for (uint32_t t = 0; t < C->P.T; ++t)
+    if (win->tile_offsets[t] == win->tile_offsets[t + 1] && !(final_tiles && final_tiles[t]))
+      return gg_fail(GG_ERR_INVALID, "%s: tile %u is not final and its window holds no record", what, t);
+  hipStream_t s = (hipStream_t)stream;
+  if (gg_status st = gg_coherent_begin(ctx, win, access_out_dev, stream)) return st;
+  // from here a failure leaves no begun run: a begun run over the first
+  // window alone would take the end of each window for the end of a trace
+  auto install = [&]() -> gg_status {
+    if (gg_status st = win_upload(ctx, what, win, final_tiles, s)) return st;
+    cs_set(C->S.win, C->win_dev);
+    const uint64_t w0[WN_HDR] = {~0ull, ~0ull};
+    GG_HIP(hipMemcpyAsync(C->win_dev, w0, sizeof(w0), hipMemcpyHostToDevice, s));
+    GG_HIP(hipMemcpyAsync(C->Sd, &C->S, sizeof(CS), hipMemcpyHostToDevice, s));
+    launch_window_install(C->P, C->S, win->addr_dev, win->meta_dev, C->offs_dev, C->win_fin_dev, 0, C->win_bad_dev, s);
+    GG_HIP(hipGetLastError());
+    GG_HIP(hipStreamSynchronize(s));
+    return GG_OK;
+  };
+  if (gg_status st = install()) { C->begun = false; C->windowed = false; C->S.win = nullptr; return st; }
+  C->windowed = true;
+  C->drv = gg_coh_state::DRV_DEVICE;                 // only gg_coherent_advance drives a windowed run
+  return GG_OK;
+}
+
+gg_status gg_coherent_next_window(gg_ctx* ctx, const gg_trace* win, uint64_t* access_out_dev, const uint8_t* final_tiles,
+                                  void* stream)
+{
+  const char* const what = "gg_coherent_next_window";
+  GG_NOT_ATAC(ctx, what);
+  if (!ctx || !win || !win->tile_offsets) return gg_fail(GG_ERR_INVALID, "%s: NULL argument", what);
+  gg_coh_state* C = ctx->coh;
+  if (!C || !C->begun || !C->windowed) return gg_fail(GG_ERR_INVALID, "%s: gg_coherent_begin_window first", what);
+  hipSetDevice(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  GG_HIP(hipStreamSynchronize(ctx->last_stream));
+  uint64_t done = 0;
+  uint32_t err = 0;
+  GG_HIP(hipMemcpy(&done, C->S.qs + QS_DONE, sizeof(done), hipMemcpyDeviceToHost));
+  GG_HIP(hipMemcpy(&err, ctx->err_dev, sizeof(err), hipMemcpyDeviceToHost));
+  if ((done & 3) || err)
+    return gg_fail(GG_ERR_INVALID, "%s: the run is not at the device loop's clean point (it is over or has failed); "
+                                   "a window goes in after begin or a paused gg_coherent_advance", what);
+  if (gg_status st = win_upload(ctx, what, win, final_tiles, s)) return st;
+  launch_window_install(C->P, C->S, win->addr_dev, win->meta_dev, C->offs_dev, C->win_fin_dev, 1, C->win_bad_dev, s);
+  GG_HIP(hipGetLastError());
+  uint32_t bad[2] = {0, 0};
+  GG_HIP(hipMemcpyAsync(bad, C->win_bad_dev, sizeof(bad), hipMemcpyDeviceToHost, s));
+  GG_HIP(hipStreamSynchronize(s));
+  if (bad[0]) {
+    const uint32_t t = bad[1] - 1;
+    const char* why = (bad[0] & WB_STATE)  ? "a tile stands past the end of its window"
+                    : (bad[0] & WB_EMPTY)  ? "an unfinished tile's window holds no record"
+                    : (bad[0] & WB_RECORD) ? "a window's first record is not the record its tile stands on (addr or meta)"
+                    : (bad[0] & WB_FINAL)  ? "a final tile made non-final, or with another number of records left"
+                                           : "a finished tile's range is not empty";
+    return gg_fail(GG_ERR_INVALID, "%s: %s (first at tile %u); nothing changed", what, why, t);
+  }
+  const uint64_t hor0 = ~0ull;
+  GG_HIP(hipMemcpyAsync(C->win_dev + WN_HOR, &hor0, sizeof(hor0), hipMemcpyHostToDevice, s));
+  launch_window_install(C->P, C->S, win->addr_dev, win->meta_dev, C->offs_dev, C->win_fin_dev, 2, C->win_bad_dev, s);
+  GG_HIP(hipGetLastError());
+  cs_set(C->S.addr, win->addr_dev); cs_set(C->S.meta, win->meta_dev); cs_set(C->S.out, access_out_dev);
+  GG_HIP(hipMemcpyAsync(C->Sd, &C->S, sizeof(CS), hipMemcpyHostToDevice, s));
+  GG_HIP(hipStreamSynchronize(s));                     // the old arrays are the caller's again
+  C->n_records = win->num_records;
+  C->offs_host.assign(win->tile_offsets, win->tile_offsets + C->P.T + 1);
+  ctx->last_stream = s;
+  return GG_OK;
+}
+
+gg_status gg_coherent_window_state(gg_ctx* ctx, uint64_t* consumed, uint64_t* min_records)
+{
+  const char* const what = "gg_coherent_window_state";
+  GG_NOT_ATAC(ctx, what);
+  if (!ctx) return gg_fail(GG_ERR_INVALID, "%s: NULL argument", what);
+  gg_coh_state* C = ctx->coh;
+  if (!C || !C->begun || !C->windowed) return gg_fail(GG_ERR_INVALID, "%s: gg_coherent_begin_window first", what);
+  hipSetDevice(ctx->device);
+  hipStream_t s = ctx->last_stream;
+  const uint32_t T = C->P.T;
+  GG_HIP(hipMemsetAsync(C->win_state_dev, 0, sizeof(uint64_t) * 2 * T, s));
+  launch_window_state(C->P, C->S, C->win_state_dev, C->win_state_dev + T, s);
+  GG_HIP(hipGetLastError());
+  GG_HIP(hipStreamSynchronize(s));
+  if (consumed) GG_HIP(hipMemcpy(consumed, C->win_state_dev, sizeof(uint64_t) * T, hipMemcpyDeviceToHost));
+  if (min_records) GG_HIP(hipMemcpy(min_records, C->win_state_dev + T, sizeof(uint64_t) * T, hipMemcpyDeviceToHost));
+  return GG_OK;
 }
 
 // ---- gg_coherent_run_many: independent runs side by side in one set of
@@ -1275,6 +1448,10 @@ static gg_status many_validate(const char* what, gg_ctx* const* ctxs, uint32_t n
       return gg_fail(shard_code, "%s: context %u does not own every shard (shard range [%u, %u) of %u)",
                      what, i, c.shard_begin, c.shard_end, K);
   }
+  for (uint32_t i = 0; i < n; ++i)
+    if (gg_coh_windowed(ctxs[i]))
+      return gg_fail(GG_ERR_UNSUPPORTED, "%s: context %u has a run fed in windows (gg_coherent_begin_window): "
+                                         "gg_coherent_advance and gg_coherent_next_window drive it", what, i);
   if (need_begun)
     for (uint32_t i = 0; i < n; ++i) {
       const gg_coh_state* C = ctxs[i]->coh;
@@ -1605,6 +1782,9 @@ gg_status snap_valid(gg_ctx* ctx, const char* what)
   gg_coh_state* C = ctx->coh;
   if (!C || !C->begun) return gg_fail(GG_ERR_INVALID, "%s: gg_coherent_begin or gg_coherent_restore first", what);
   if (gg_status st = coh_owns_all(ctx, GG_ERR_UNSUPPORTED, what)) return st;
+  if (C->windowed)
+    return gg_fail(GG_ERR_UNSUPPORTED, "%s: a run fed in windows (gg_coherent_begin_window) has no snapshot: "
+                                       "the trace it continues on is not there yet", what);
   if (C->drv == gg_coh_state::DRV_HOST)
     return gg_fail(GG_ERR_INVALID, "%s: a run driven by gg_coherent_quantum / the round is not at the device loop's "
                                    "clean point (after begin, an advance or a restore)", what);

@@ -424,6 +424,9 @@ extern "C" {
 gg_status gg_core_model_run(gg_ctx* ctx, const gg_trace* tr, const uint64_t* access_out_dev, void* stream)
 {
   if (!ctx || !tr || !tr->tile_offsets) return gg_fail(GG_ERR_INVALID, "gg_core_model_run: NULL argument");
+  if (gg_coh_windowed(ctx))
+    return gg_fail(GG_ERR_UNSUPPORTED, "gg_core_model_run: the context's coherent run is fed in windows "
+                                       "(gg_coherent_begin_window); the core model needs the whole trace");
   const uint32_t T = ctx->cfg.num_tiles;
   const uint64_t* off = tr->tile_offsets;
   if (off[0] != 0) return gg_fail(GG_ERR_INVALID, "gg_core_model_run: tile_offsets[0] != 0");

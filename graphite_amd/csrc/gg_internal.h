@@ -33,6 +33,7 @@
 #define GG_DERR_SAMPLES 16u // the statistics trace's sample buffer is full (gg_stats.hip)
 #define GG_DERR_SHARERS 32u // the statistics trace's scan met a directory entry with more sharers than tiles
 #define GG_DERR_MT_CAP 64u  // Mode P miss-type tracking: a (tile, L1-D set) slice of the address table is full (gg_modep_mt.h)
+#define GG_DERR_WINDOW 128u // a windowed coherent run: a tile reached the end of a window that is not the end of its trace
 
 // Geometry derived from gg_config (cache.cc:44, cache_hash_fn.h:11).
 struct gg_geom {
@@ -216,3 +217,4 @@ bool      gg_stats_on(const gg_ctx* ctx);                 // a trace is configur
 gg_status gg_stats_begin(gg_ctx* ctx, hipStream_t s);     // gg_coherent_begin: the configured trace, no samples
 gg_status gg_stats_slot(gg_ctx* ctx, hipStream_t s, uint32_t L);   // gg_coherent_run: the scan launch of slot L
 uint64_t  gg_coh_generation(gg_ctx* ctx);    // bumped by every gg_coherent_begin (0: none yet)
+bool      gg_coh_windowed(const gg_ctx* ctx); // the begun run is fed its trace in windows (gg_coherent_begin_window)

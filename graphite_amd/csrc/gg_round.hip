@@ -160,6 +160,11 @@ gg_status round_pack(gg_ctx* ctx, uint32_t W, uint32_t R, uint64_t q, gg_round_i
   if (c.shard_begin != R * per || k1 != (R + 1) * per)
     return gg_fail(GG_ERR_INVALID, "rank %u must own shards [%u, %u), the context owns [%u, %u)", R, R * per,
                    (R + 1) * per, c.shard_begin, k1);
+  // a run fed in windows is driven by gg_coherent_advance alone (it owns every
+  // shard: no peer waits for this rank), refused before anything is enqueued
+  if (gg_coh_windowed(ctx))
+    return gg_fail(GG_ERR_INVALID, "this run is fed in windows and driven by gg_coherent_advance "
+                                   "(gg_coherent_begin_window): gg_coherent_quantum and the round keep different state words");
   hipSetDevice(ctx->device);
   // These checks and the first round's buffers fail before anything is
   // enqueued: they depend only on arguments and on gg_coherent_begin having
@@ -269,7 +274,7 @@ gg_status gg_round_unpack(gg_ctx* ctx, gg_round_io* io)
   GG_NOT_ATAC(ctx, "gg_round_unpack");
   if (!ctx || !io) return gg_fail(GG_ERR_INVALID, "NULL argument");
   RoundBufs* B = bufs_of(ctx);
-  if (!B || !ctx->coh) return gg_fail(GG_ERR_INVALID, "gg_round_pack first");
+  if (!B || !ctx->coh || gg_coh_windowed(ctx)) return gg_fail(GG_ERR_INVALID, "gg_round_pack first");
   hipSetDevice(ctx->device);
   hipStream_t s = ctx->last_stream;
   const int W = B->world;
@@ -326,7 +331,7 @@ gg_status gg_round_finish(gg_ctx* ctx, gg_round_io* io)
   GG_NOT_ATAC(ctx, "gg_round_finish");
   if (!ctx || !io) return gg_fail(GG_ERR_INVALID, "NULL argument");
   RoundBufs* B = bufs_of(ctx);
-  if (!B || !ctx->coh) return gg_fail(GG_ERR_INVALID, "gg_round_pack first");
+  if (!B || !ctx->coh || gg_coh_windowed(ctx)) return gg_fail(GG_ERR_INVALID, "gg_round_pack first");
   hipSetDevice(ctx->device);
   // a failed import is this rank's alone (its peers decide from the same
   // words and go on): pending, as in unpack

@@ -35,6 +35,14 @@
 //   gg_replay --coherent ... --restore FILE
 //       continues that run to its end (the same options as the first leg) and
 //       prints what the uninterrupted run prints
+//   gg_replay --coherent ... --window RECORDS
+//       the same run with the trace made window by window while it runs
+//       (gg_coherent_begin_window / _next_window): every tile is handed
+//       max(RECORDS, what gg_coherent_window_state asks for) records at a time,
+//       generated from the tile's first unconsumed record; prints exactly what
+//       the run without --window prints.  A demonstration of the calls, not a
+//       fast path: the windows start at another record in every tile, so each
+//       hand-over is one generator launch per tile
 //   gg_replay --stats-trace-selftest
 //       prints both files' text for a fixed three-sample input (no GPU needed)
 //   gg_replay --format-table FILE...
@@ -80,7 +88,7 @@ int main(int argc, char** argv)
   uint32_t miss_lines = 0;
   uint64_t per_tile = 100000;
   std::string trace, id_file, stats_dir, ckpt_out, ckpt_in;
-  uint64_t ckpt_quantum = 0;
+  uint64_t ckpt_quantum = 0, window = 0;
   uint64_t sampling_interval = 10000, max_samples = 4096;
   uint32_t protocol = GG_PROTO_MSI;
   int ranks = 1, rank = 0;
@@ -100,6 +108,7 @@ int main(int argc, char** argv)
     else if (a == "--checkpoint") ckpt_out = next();
     else if (a == "--checkpoint-quantum") ckpt_quantum = std::strtoull(next(), nullptr, 0);
     else if (a == "--restore") ckpt_in = next();
+    else if (a == "--window") window = std::strtoull(next(), nullptr, 0);
     else if (a == "--sampling-interval") sampling_interval = std::strtoull(next(), nullptr, 0);
     else if (a == "--max-samples") max_samples = std::strtoull(next(), nullptr, 0);
     else if (a == "--protocol") {
@@ -249,6 +258,10 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "gg_replay: --checkpoint / --restore are for a single-process run\n");
         return 2;
       }
+      if (window && (!id_file.empty() || !ckpt_out.empty() || !ckpt_in.empty())) {
+        std::fprintf(stderr, "gg_replay: --window is for a single-process run without --checkpoint / --restore\n");
+        return 2;
+      }
       if (!id_file.empty()) {
         // one process per GPU: the RCCL communicator of `ranks` processes
         if (rank < 0 || rank >= ranks || shards % (uint32_t)ranks) {
@@ -281,19 +294,53 @@ int main(int argc, char** argv)
         cfg.shard_end = ((uint32_t)rank + 1) * (shards / ranks);
       }
       Backend be(cfg);
-      const uint64_t n = (uint64_t)tiles * per_tile;
+      const uint64_t n = window ? 0 : (uint64_t)tiles * per_tile;
       DeviceBuffer<uint64_t> addr;
       DeviceBuffer<uint32_t> meta;
       addr.resize(n); meta.resize(n);
-      check(gg_gen_hotspot_trace(addr.p, meta.p, 0, tiles, per_tile, 0, lines_log2, 26, hot_lines, 51, nullptr),
-            "gg_gen_hotspot_trace");
+      if (!window)
+        check(gg_gen_hotspot_trace(addr.p, meta.p, 0, tiles, per_tile, 0, lines_log2, 26, hot_lines, 51, nullptr),
+              "gg_gen_hotspot_trace");
       std::vector<uint64_t> offs(tiles + 1);
       for (uint32_t t = 0; t <= tiles; ++t) offs[t] = (uint64_t)t * per_tile;
       gg_trace tr{addr.p, meta.p, offs.data(), n};
       if (!stats_dir.empty())
         check(gg_stats_trace_configure(be.ctx(), GG_ST_NETWORK_UTILIZATION | GG_ST_CACHE_LINE_REPLICATION, sampling_interval,
                                        max_samples), "gg_stats_trace_configure");
-      if (!ckpt_out.empty() || !ckpt_in.empty()) {
+      if (window) {
+        // the trace in windows: each tile's next records are generated when the
+        // run asks for them; the window in use stays until the next is installed
+        std::vector<uint64_t> consumed(tiles, 0), need(tiles, 0), woffs(tiles + 1, 0);
+        std::vector<uint8_t> fin(tiles, 0);
+        DeviceBuffer<uint64_t> wa[2];
+        DeviceBuffer<uint32_t> wm[2];
+        DeviceBuffer<uint64_t> ww[2];                     // the windows' access words (bound, not printed)
+        uint64_t handovers = 0;
+        for (int cur = 0;; cur ^= 1, ++handovers) {
+          for (uint32_t t = 0; t < tiles; ++t) {
+            const uint64_t left = per_tile - consumed[t];
+            const uint64_t cnt = fin[t] ? left : std::min(left, std::max(window, need[t]));   // (a final tile stays final)
+            fin[t] = cnt == left;
+            woffs[t + 1] = woffs[t] + cnt;
+          }
+          const uint64_t wn = woffs[tiles];
+          wa[cur].resize(wn ? wn : 1); wm[cur].resize(wn ? wn : 1); ww[cur].resize(wn ? wn : 1);
+          for (uint32_t t = 0; t < tiles; ++t)
+            if (woffs[t + 1] > woffs[t])
+              check(gg_gen_hotspot_trace(wa[cur].p + woffs[t], wm[cur].p + woffs[t], t, 1, woffs[t + 1] - woffs[t],
+                                         consumed[t], lines_log2, 26, hot_lines, 51, nullptr), "gg_gen_hotspot_trace");
+          gg_trace w{wa[cur].p, wm[cur].p, woffs.data(), wn};
+          if (handovers == 0) check(gg_coherent_begin_window(be.ctx(), &w, ww[cur].p, fin.data(), nullptr), "gg_coherent_begin_window");
+          else check(gg_coherent_next_window(be.ctx(), &w, ww[cur].p, fin.data(), nullptr), "gg_coherent_next_window");
+          uint64_t nq = 0;
+          int done = 0;
+          check(gg_coherent_advance(be.ctx(), ~0ull, &nq, &done), "gg_coherent_advance");
+          if (done == 1) break;
+          check(gg_coherent_window_state(be.ctx(), consumed.data(), need.data()), "gg_coherent_window_state");
+        }
+        std::fprintf(stderr, "gg_replay: %llu windows handed over\n", (unsigned long long)handovers);
+      }
+      else if (!ckpt_out.empty() || !ckpt_in.empty()) {
         // a run in legs: the access words travel with the snapshot
         DeviceBuffer<uint64_t> words;
         words.resize(n);

@@ -682,6 +682,76 @@ gg_status gg_coherent_snapshot_size(gg_ctx* ctx, uint64_t* bytes);
 gg_status gg_coherent_snapshot(gg_ctx* ctx, void* host_buf, uint64_t cap, uint64_t* bytes);
 gg_status gg_coherent_restore(gg_ctx* ctx, const gg_trace* trace, uint64_t* access_out_dev,
                               const void* host_buf, uint64_t bytes, void* stream);
+/* A coherent run fed its trace in windows: the trace
+ * and the access words need not be resident, or exist, before the first
+ * launch.  Each tile is given a window of its records that starts at its
+ * first unconsumed record and holds at least that one; a tile is final once
+ * its window runs to the end of its trace.  The run pauses at a quantum
+ * boundary before any quantum in which a tile that is not final could consume
+ * the last record of its window; the caller installs the next windows and the
+ * run goes on.  The results (access words, tile statistics, cache, NoC and
+ * protocol counters, run info, miss types, statistics-trace samples) do not
+ * depend on where the windows were cut, or on whether the trace was windowed.
+ *
+ * gg_coherent_begin_window is gg_coherent_begin with a first window: win's
+ * tile_offsets index its own arrays, access_out_dev has win->num_records
+ * words (or NULL).  final_tiles[num_tiles] (host): != 0 where the tile's
+ * window runs to the end of its trace; NULL: no tile is final.  A tile with an
+ * empty window must be final (GG_ERR_INVALID).  The context must own every
+ * shard (GG_ERR_UNSUPPORTED); with cfg.l1d_data_cycles == 0 a record can cost
+ * no time and no window bounds a quantum: GG_ERR_UNSUPPORTED.  Only
+ * gg_coherent_advance drives the run; it takes the per-step launches on every
+ * mesh size.
+ *
+ * gg_coherent_advance on a windowed run can return *done =
+ * GG_ADV_NEED_WINDOW: paused at the device loop's clean point because the
+ * quantum picked to run next (*next_quantum, as at a pause) is not safe for
+ * some tile that is not final.  Windows already too short for the next
+ * quantum give it at once, with no launch.  A stop_quantum reached at the same
+ * boundary returns *done = 0 as ever, and the next advance asks for the
+ * windows.  A run that is not windowed never sees the value.
+ *
+ * gg_coherent_window_state: consumed[t] = the records tile t has consumed
+ * since begin (the caller's index of the tile's first unconsumed record);
+ * min_records[t] = the records the next window of a tile that is not final
+ * must hold, counted from the first unconsumed record up to the window's last
+ * record that is neither a GG_META_CONT line nor a BARRIER record, for the
+ * next quantum to run at all (0 for final and finished tiles).  CONT lines and
+ * BARRIER records after that record may follow in the window; they do not
+ * count.  Both arrays are [num_tiles] on the host; either may be NULL.
+ * Synchronizes.
+ *
+ * gg_coherent_next_window hands the next windows over.  It is valid only at
+ * the clean point of a windowed run that is paused (*done 0 or
+ * GG_ADV_NEED_WINDOW) or not yet advanced.  Tile t's records in win begin at
+ * the tile's first unconsumed record, the record consumed[t] of its trace; a
+ * tile that was final and has finished has an empty range.  A device kernel
+ * rebases every tile's position to the new arrays, checks that the first
+ * record of every unfinished tile equals, in addr and meta, the record the
+ * tile stands on (a blocked tile's pending record, whose access word is
+ * still to be written, goes to the new access_out_dev), and stores the final
+ * flags.  GG_ERR_INVALID with nothing changed: a first record that differs,
+ * an unfinished tile with an empty range, a final tile made non-final or
+ * given another number of remaining records, a finished tile with records, a
+ * run that is over or has failed, a run that is not windowed.  After the call
+ * returns the old arrays belong to the caller again; their access words for
+ * consumed records are final, and the word of record consumed[t] + i of tile t
+ * is word i of the tile's range in the buffer bound while it was consumed.
+ *
+ * The backstop: should a tile that is not final ever reach the end of its
+ * window, the run ends with GG_ERR_STATE ("window exhausted"), never with
+ * *done = 1 and never with a result.
+ * On a windowed run gg_coherent_snapshot / _snapshot_size,
+ * gg_coherent_advance_many, gg_coherent_run_many and gg_core_model_run (it
+ * needs the whole trace) return GG_ERR_UNSUPPORTED; gg_coherent_quantum and
+ * gg_round_* return GG_ERR_INVALID as for any advance-driven run.  A later
+ * gg_coherent_begin, _run or _restore on the context starts an ordinary run. */
+#define GG_ADV_NEED_WINDOW 3
+gg_status gg_coherent_begin_window(gg_ctx* ctx, const gg_trace* win, uint64_t* access_out_dev,
+                                   const uint8_t* final_tiles, void* stream);
+gg_status gg_coherent_next_window(gg_ctx* ctx, const gg_trace* win, uint64_t* access_out_dev,
+                                  const uint8_t* final_tiles, void* stream);
+gg_status gg_coherent_window_state(gg_ctx* ctx, uint64_t* consumed, uint64_t* min_records);
 /* The coherent mode over ranks (one process per GPU), RCCL over xGMI.
  * nccl_comm is an ncclComm_t (RCCL) of W ranks; rank r's context must own
  * logical shards [r*K/W, (r+1)*K/W) (cfg.shard_begin / shard_end, K =
