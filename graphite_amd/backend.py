@@ -67,7 +67,30 @@ EXPORTS = ["gg_abi_version", "gg_last_error", "gg_config_default", "gg_create", 
            "gg_cache_track_miss_types", "gg_cache_get_miss_types",
            "gg_coherent_advance", "gg_coherent_snapshot_size", "gg_coherent_snapshot", "gg_coherent_restore",
            "gg_coherent_advance_many",
-           "gg_coherent_begin_window", "gg_coherent_next_window", "gg_coherent_window_state"]
+           "gg_coherent_begin_window", "gg_coherent_next_window", "gg_coherent_window_state",
+           "gg_traffic_params_default", "gg_gen_network_traffic", "gg_noc_latency_stats", "gg_noc_synthetic_run"]
+
+# synthetic network traffic (gg_gen_network_traffic): GG_TP_* patterns, GG_NLS_* words of the reduction
+TRAFFIC_PATTERNS = ["uniform_random", "bit_complement", "shuffle", "transpose", "tornado", "nearest_neighbor"]
+(TP_UNIFORM_RANDOM, TP_BIT_COMPLEMENT, TP_SHUFFLE, TP_TRANSPOSE, TP_TORNADO, TP_NEAREST_NEIGHBOR) = range(6)
+NETPACKET_BYTES = 64     # GG_NETPACKET_BYTES
+NLS_FIELDS = ["packets", "self_packets", "latency_ps", "zero_load_ps", "contention_ps", "max_latency_ps",
+              "last_arrival_ps"]
+(NLS_PACKETS, NLS_SELF_PACKETS, NLS_LATENCY_PS, NLS_ZERO_LOAD_PS, NLS_CONTENTION_PS, NLS_MAX_LATENCY_PS,
+ NLS_LAST_ARRIVAL_PS) = range(7)
+NLS_HIST = 8             # + bit length of the latency in ps, 65 bins
+NUM_NLS = NLS_HIST + 65
+
+
+class TrafficParams(ctypes.Structure):
+    """gg_traffic_params: the synthetic_network benchmark's -p / -s / -l / -N and a seed."""
+    _fields_ = [("pattern", ctypes.c_uint32), ("packet_bytes", ctypes.c_uint32), ("offered_load", ctypes.c_double),
+                ("packets_per_tile", ctypes.c_uint64), ("seed", ctypes.c_uint64)]
+
+    def __init__(self, pattern=TP_UNIFORM_RANDOM, packet_bytes=8, offered_load=0.1, packets_per_tile=10000, seed=0):
+        if isinstance(pattern, str):
+            pattern = TRAFFIC_PATTERNS.index(pattern)
+        super().__init__(pattern, packet_bytes, offered_load, packets_per_tile, seed)
 
 # statistics trace (gg_stats_trace_*): GG_ST_* statistics bits, GG_STF_* sample fields
 ST_NETWORK_UTILIZATION, ST_CACHE_LINE_REPLICATION = 1, 2
@@ -186,6 +209,13 @@ def load():
     L.gg_coherent_next_window.argtypes = [vp, ctypes.POINTER(_Trace), vp, vp, vp]
     L.gg_coherent_window_state.argtypes = [vp, vp, vp]
     for name in ["gg_coherent_begin_window", "gg_coherent_next_window", "gg_coherent_window_state"]:
+        getattr(L, name).restype = i32
+    L.gg_traffic_params_default.argtypes = [ctypes.POINTER(TrafficParams)]
+    L.gg_traffic_params_default.restype = None
+    L.gg_gen_network_traffic.argtypes = [ctypes.POINTER(TrafficParams), u32, ctypes.c_double, vp, vp, vp, vp, vp, vp]
+    L.gg_noc_latency_stats.argtypes = [ctypes.POINTER(_Packets), ctypes.POINTER(_PacketOut), vp, vp]
+    L.gg_noc_synthetic_run.argtypes = [vp, ctypes.POINTER(TrafficParams), vp, vp]
+    for name in ["gg_gen_network_traffic", "gg_noc_latency_stats", "gg_noc_synthetic_run"]:
         getattr(L, name).restype = i32
     for name in ["gg_kernel_stats", "gg_shard_map", "gg_coherent_begin", "gg_coherent_quantum", "gg_coherent_export",
                  "gg_coherent_import", "gg_coherent_run", "gg_coherent_get_stats", "gg_gen_hotspot_trace",
@@ -357,6 +387,15 @@ class Backend:
         out = np.zeros(self.cfg.num_tiles * NUM_NET_COUNTERS, np.uint64)
         _check(load().gg_noc_get_counters(self.h, out.ctypes.data_as(ctypes.c_void_p)))
         return out.reshape(self.cfg.num_tiles, NUM_NET_COUNTERS)
+
+    def noc_synthetic_run(self, params, stream=None):
+        """gg_noc_synthetic_run: generate params' traffic for this context's
+        tiles, route it (continuing from the queue state) and reduce it;
+        returns the NUM_NLS words (NLS_*)."""
+        stats = np.zeros(NUM_NLS, np.uint64)
+        _check(load().gg_noc_synthetic_run(self.h, ctypes.byref(params), stats.ctypes.data_as(ctypes.c_void_p),
+                                           _stream(stream)))
+        return stats
 
     def noc_set_atac(self, params):
         """gg_noc_set_atac: the ATAC settings (config.AtacParams) of a NET_ATAC
@@ -762,6 +801,38 @@ def gen_stress_trace(addr, meta, tile_begin, tiles, per_tile, num_tiles, first=0
     """Fill device tensors with the configs[4] coherent stress trace."""
     _check(load().gg_gen_stress_trace(_ptr(addr), _ptr(meta), tile_begin, tiles, per_tile, first, lines_log2,
                                       base_shift, num_tiles, pool_lines, pool_frac256, _stream(stream)))
+
+
+def gen_network_traffic(params, num_tiles, frequency_ghz, src, dst, length_bits, time_ps, last_cycle=None,
+                        stream=None):
+    """gg_gen_network_traffic: fill device tensors (int32 x 3, int64; num_tiles x
+    params.packets_per_tile entries, tile-major) with the synthetic_network
+    benchmark's packets; last_cycle (int64, num_tiles) receives the cycle of
+    every tile's last packet."""
+    import torch
+    n = num_tiles * params.packets_per_tile
+    for t, dt in ((src, torch.int32), (dst, torch.int32), (length_bits, torch.int32), (time_ps, torch.int64)):
+        _need_dev(t, dt, n)
+    if last_cycle is not None:
+        _need_dev(last_cycle, torch.int64, num_tiles)
+    _check(load().gg_gen_network_traffic(ctypes.byref(params), num_tiles, frequency_ghz, _ptr(src), _ptr(dst),
+                                         _ptr(length_bits), _ptr(time_ps), _ptr(last_cycle), _stream(stream)))
+
+
+def noc_latency_stats(src, dst, length_bits, time_ps, arrival, zero_load, contention, stream=None):
+    """gg_noc_latency_stats: the NUM_NLS words (NLS_*) of a routed batch, reduced
+    on the device (the tensors of Backend.noc_route_batch)."""
+    import torch
+    n = src.numel()
+    for t, dt in ((src, torch.int32), (dst, torch.int32), (length_bits, torch.int32), (time_ps, torch.int64),
+                  (arrival, torch.int64), (zero_load, torch.int64), (contention, torch.int64)):
+        _need_dev(t, dt, n)
+    pk = _Packets(src.data_ptr(), dst.data_ptr(), length_bits.data_ptr(), time_ps.data_ptr(), n)
+    out = _PacketOut(arrival.data_ptr(), zero_load.data_ptr(), contention.data_ptr())
+    stats = np.zeros(NUM_NLS, np.uint64)
+    _check(load().gg_noc_latency_stats(ctypes.byref(pk), ctypes.byref(out), stats.ctypes.data_as(ctypes.c_void_p),
+                                       _stream(stream)))
+    return stats
 
 
 def split_accesses(addr, size, meta, tile_offsets, line_size=64, stream=None):

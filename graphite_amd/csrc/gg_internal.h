@@ -84,6 +84,7 @@ struct gg_noc_state;
 struct gg_coh_state;
 struct gg_stats_state;
 struct gg_atac_state;
+struct gg_synth_state;
 
 struct gg_ctx {
   gg_config cfg;
@@ -143,6 +144,8 @@ struct gg_ctx {
   void (*round_free)(void*) = nullptr;
   // statistics trace (gg_stats.hip), allocated by gg_stats_trace_configure
   gg_stats_state* stats = nullptr;
+  // packet arrays of gg_noc_synthetic_run (gg_noc_synth.hip), allocated on first use
+  gg_synth_state* synth = nullptr;
 };
 inline void* gg_round_state(gg_ctx* ctx) { return ctx->round; }
 inline void gg_round_state_set(gg_ctx* ctx, void* p, void (*f)(void*)) { ctx->round = p; ctx->round_free = f; }
@@ -218,3 +221,5 @@ gg_status gg_stats_begin(gg_ctx* ctx, hipStream_t s);     // gg_coherent_begin: 
 gg_status gg_stats_slot(gg_ctx* ctx, hipStream_t s, uint32_t L);   // gg_coherent_run: the scan launch of slot L
 uint64_t  gg_coh_generation(gg_ctx* ctx);    // bumped by every gg_coherent_begin (0: none yet)
 bool      gg_coh_windowed(const gg_ctx* ctx); // the begun run is fed its trace in windows (gg_coherent_begin_window)
+// synthetic network traffic (gg_noc_synth.hip)
+void      gg_synth_free(gg_ctx* ctx);

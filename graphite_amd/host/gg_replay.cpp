@@ -50,6 +50,11 @@
 //   gg_replay --tiles T --net M --route FILE
 //       NetworkModel::routePacket (the host mirror, broadcasts through the
 //       hop-by-hop broadcast tree) on a packet file; hops + network summaries
+//   gg_replay --tiles T --net M --synthetic-network PATTERN [--load L] [--packet-bytes S] [--packets N] [--seed X]
+//       the reference's NoC benchmark (synthetic_network.cc -p PATTERN -l L -s S
+//       -N N) generated, routed and reduced on the device (gg_noc_synthetic_run):
+//       the network summaries as --route prints them, then one line of the
+//       reduction (packets, mean / max latency, mean contention, last arrival)
 //   gg_replay --summary-selftest
 //       prints writeCacheSummary() for fixed counters (no GPU needed)
 //   gg_replay --mosi-summary FILE TILES
@@ -93,6 +98,9 @@ int main(int argc, char** argv)
   uint32_t protocol = GG_PROTO_MSI;
   int ranks = 1, rank = 0;
   uint32_t shards = 1;
+  std::string synth_pattern;
+  gg_traffic_params synth;
+  gg_traffic_params_default(&synth);
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() -> const char* { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -170,7 +178,12 @@ int main(int argc, char** argv)
                             cfg.net_model == GG_NET_EMESH_HOP_BY_HOP);
       return 0;
     }
-    else if (a == "--shards") shards = (uint32_t)std::strtoul(next(), nullptr, 0);
+    else if (a == "--synthetic-network") synth_pattern = next();
+    else if (a == "--load") synth.offered_load = std::strtod(next(), nullptr);
+    else if (a == "--packet-bytes") synth.packet_bytes = (uint32_t)std::strtoul(next(), nullptr, 0);
+    else if (a == "--packets") synth.packets_per_tile = std::strtoull(next(), nullptr, 0);
+    else if (a == "--seed") synth.seed = std::strtoull(next(), nullptr, 0);
+    else if (a == "--shards") shards =(uint32_t)std::strtoul(next(), nullptr, 0);
     else if (a == "--ranks") ranks = std::atoi(next());
     else if (a == "--rank") rank = std::atoi(next());
     else if (a == "--id-file") id_file = next();
@@ -240,6 +253,26 @@ int main(int argc, char** argv)
       writeDramSummary(std::cout, st, true, GG_QM_BASIC);
       return 0;
     } else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
+  }
+  if (!synth_pattern.empty()) {
+    try {
+      synth.pattern = trafficPattern(synth_pattern);
+      gg_config cfg;
+      gg_config_default(&cfg, tiles);
+      cfg.net_model = net;
+      Backend be(cfg);
+      const std::vector<uint64_t> stats = SyntheticNetwork(be).run(synth);
+      std::vector<uint64_t> nc((size_t)tiles * GG_NUM_NET_COUNTERS);
+      check(gg_noc_get_counters(be.ctx(), nc.data()), "gg_noc_get_counters");
+      for (uint32_t t = 0; t < tiles; ++t)
+        writeNetworkSummary(std::cout, &nc[(size_t)t * GG_NUM_NET_COUNTERS], cfg.frequency_ghz, cfg.net_model,
+                            cfg.net_model == GG_NET_EMESH_HOP_BY_HOP);
+      writeLatencyStats(std::cout, stats.data());
+    } catch (const std::exception& e) {
+      std::fprintf(stderr, "gg_replay: %s\n", e.what());
+      return 1;
+    }
+    return 0;
   }
   if (coherent) {
     ncclComm_t comm = nullptr;

@@ -12,6 +12,9 @@
 //                                + __processReceivedPacket, batched through
 //                                gg_noc_route_batch; Hop carries the same fields
 //                                (network_model.h:45-63)
+//   graphite_amd::SyntheticNetwork  the NoC benchmark
+//                                (tests/benchmarks/synthetic_network/synthetic_network.cc)
+//                                through gg_noc_synthetic_run
 //
 // Errors: the reference aborts through LOG_ASSERT_ERROR (common/misc/log.h:112-135);
 // the mirror throws graphite_amd::Error carrying the ABI status and message.
@@ -973,6 +976,45 @@ class NetworkModel {
   Backend& _be;
   DeviceBuffer<uint32_t> _s, _d, _l;
   DeviceBuffer<uint64_t> _t, _a, _z, _c, _ba, _bz, _bc;
+};
+
+// The reference's NoC benchmark (tests/benchmarks/synthetic_network/synthetic_network.cc):
+// its -p names (:56-83 parses them) -> GG_TP_*.  Unknown names are an error,
+// as its LOG_PRINT_ERROR("Unrecognized traffic pattern").
+inline uint32_t trafficPattern(const std::string& name)
+{
+  static const char* const names[GG_NUM_TRAFFIC_PATTERNS] = {"uniform_random", "bit_complement", "shuffle",
+                                                             "transpose", "tornado", "nearest_neighbor"};
+  for (uint32_t k = 0; k < GG_NUM_TRAFFIC_PATTERNS; ++k)
+    if (name == names[k]) return k;
+  throw std::invalid_argument("Unrecognized traffic pattern (" + name + ")");
+}
+
+// One line of gg_noc_latency_stats' words: packets, mean and maximum latency,
+// mean contention, last arrival (the means over the packets with src != dst).
+inline void writeLatencyStats(std::ostream& out, const uint64_t* s)
+{
+  const double n = s[GG_NLS_PACKETS] ? (double)s[GG_NLS_PACKETS] : 1.0;
+  std::ostringstream os;                 // (the caller's stream keeps its format flags)
+  os << "Synthetic Network: packets " << s[GG_NLS_PACKETS] << " self " << s[GG_NLS_SELF_PACKETS] << std::fixed
+     << std::setprecision(3) << " mean latency (ps) " << (double)s[GG_NLS_LATENCY_PS] / n << " max latency (ps) "
+     << s[GG_NLS_MAX_LATENCY_PS] << " mean contention (ps) " << (double)s[GG_NLS_CONTENTION_PS] / n
+     << " last arrival (ps) " << s[GG_NLS_LAST_ARRIVAL_PS];
+  out << os.str() << std::endl;
+}
+
+// The benchmark on a context: generate, route, reduce (gg_noc_synthetic_run).
+class SyntheticNetwork {
+ public:
+  explicit SyntheticNetwork(Backend& be) : _be(be) {}
+  std::vector<uint64_t> run(const gg_traffic_params& p, hipStream_t stream = nullptr)
+  {
+    std::vector<uint64_t> s(GG_NUM_NLS);
+    check(gg_noc_synthetic_run(_be.ctx(), &p, s.data(), stream), "gg_noc_synthetic_run");
+    return s;
+  }
+ private:
+  Backend& _be;
 };
 
 }  // namespace graphite_amd

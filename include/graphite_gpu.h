@@ -38,6 +38,10 @@
  *                              (network_model.cc:228-316, router_model.cc:120-145)
  *   gg_queue_delay_batch       QueueModelHistoryTree::computeQueueDelay
  *                              (common/shared_models/queue_models/queue_model_history_tree.cc:44-126)
+ *   gg_gen_network_traffic     the send loop and the six traffic patterns of
+ *                              tests/benchmarks/synthetic_network/synthetic_network.cc:140-359
+ *   gg_noc_latency_stats       its result: packets, latency and contention of a batch
+ *   gg_noc_synthetic_run       the benchmark in one call on a context
  *
  * Conventions: every function returns a gg_status (0 = OK, negative = error);
  * no exception crosses the ABI; pointers named *_dev are HIP device pointers,
@@ -959,6 +963,70 @@ gg_status gg_gen_stress_trace(uint64_t* addr_dev, uint32_t* meta_dev, uint32_t t
 gg_status gg_gen_hotspot_trace(uint64_t* addr_dev, uint32_t* meta_dev, uint32_t tile_begin, uint32_t tiles,
                                uint64_t per_tile, uint64_t first, uint32_t lines_log2, uint32_t base_shift,
                                uint32_t hot_lines, uint32_t hot_frac256, void* stream);
+
+/* Synthetic network traffic: the reference's NoC benchmark
+ * tests/benchmarks/synthetic_network/synthetic_network.cc as an open-loop
+ * packet batch.  Its sends are never held back by the receive window
+ * (:177-208) and the lax barrier changes no timestamp, so the batch API
+ * reproduces it once the packets exist; Random<double> (seeded with time() in
+ * the reference) is SplitMix64 here.                                        */
+enum { GG_TP_UNIFORM_RANDOM = 0, GG_TP_BIT_COMPLEMENT, GG_TP_SHUFFLE, GG_TP_TRANSPOSE,
+       GG_TP_TORNADO, GG_TP_NEAREST_NEIGHBOR, GG_NUM_TRAFFIC_PATTERNS };
+#define GG_NETPACKET_BYTES 64u   /* sizeof(NetPacket), network.h:27-55, x86-64 */
+typedef struct gg_traffic_params {
+  uint32_t pattern;          /* GG_TP_*                         (-p) */
+  uint32_t packet_bytes;     /* payload bytes, default 8        (-s) */
+  double   offered_load;     /* packets / tile / cycle, (0, 1]  (-l) */
+  uint64_t packets_per_tile; /* default 10000                   (-N) */
+  uint64_t seed;
+} gg_traffic_params;
+/* pattern uniform_random, 8 bytes, load 0.1, 10000 packets, seed 0. */
+void      gg_traffic_params_default(gg_traffic_params* p);
+/* Fills a tile-major batch: packet k of tile t at index t * N + k, N =
+ * packets_per_tile; the four arrays hold num_tiles * N entries.
+ *  - Destinations (synthetic_network.cc:232-359).  The mesh is w =
+ *    floor(sqrt(T)), h = ceil(T / w); w * h != T is GG_ERR_INVALID (:347).
+ *    bit_complement and shuffle need a power-of-two T (:290, :299), else
+ *    GG_ERR_INVALID.  transpose, tornado and nearest_neighbor as written,
+ *    non-square meshes included.  uniform_random: the LCG matrix
+ *    send_matrix[i][j] (:238-252) equals orbit[i + j] with orbit[0] = T / 2,
+ *    orbit[k + 1] = (13 * orbit[k] + 5) % T, so tile t sends packet k to
+ *    orbit[(k % T) + t]; where a row or column is no permutation (:255-279
+ *    asserts; T = 100 is such a count) GG_ERR_INVALID.
+ *  - Injection (:180, :215-218).  s_t = SplitMix64(seed) step t + 1; at cycle
+ *    c = 0, 1, ... the draw is z = SplitMix64(s_t) step c + 1, and the tile
+ *    sends iff (z >> 11) < ceil(offered_load * 2^53), until it has sent N.
+ *  - Fields.  time = c * Latency(1, frequency) ps (:206-207 adds ONE_CYCLE per
+ *    iteration); length = (GG_NETPACKET_BYTES + packet_bytes) * 8 bits
+ *    (network_model.cc:196-199, network.cc:705-708); a destination equal to
+ *    the sender is kept.  last_cycle_dev[t] (may be NULL): the cycle of tile
+ *    t's last packet.
+ * GG_ERR_INVALID: a NULL array, a load outside (0, 1], an unknown pattern,
+ * N = 0.  GG_ERR_RANGE: T * N >= 2^32 (the batch limit), N / offered_load >
+ * 2^28 expected cycles.  GG_ERR_UNSUPPORTED: uniform_random beyond 2^20 tiles
+ * (its table).  All before any launch.  A tile that reaches cycle 2^32 - 64
+ * stops: GG_ERR_RANGE.  Synchronizes the stream.                            */
+gg_status gg_gen_network_traffic(const gg_traffic_params* p, uint32_t num_tiles, double frequency_ghz,
+                                 uint32_t* src_dev, uint32_t* dst_dev, uint32_t* length_bits_dev,
+                                 uint64_t* time_ps_dev, uint64_t* last_cycle_dev /* [tiles], may be NULL */,
+                                 void* stream);
+/* One pass over a routed batch (the arrays of gg_noc_route_batch): what
+ * the benchmark's users read off Network::outputSummary (network.cc:79-89),
+ * per batch instead of per tile.  A packet with src == dst counts in
+ * GG_NLS_SELF_PACKETS only.  stats: host, GG_NUM_NLS words (word 7 is 0).
+ * Synchronizes the stream.                                                  */
+enum { GG_NLS_PACKETS = 0 /* src != dst */, GG_NLS_SELF_PACKETS, GG_NLS_LATENCY_PS /* sum of arrival - time */,
+       GG_NLS_ZERO_LOAD_PS, GG_NLS_CONTENTION_PS, GG_NLS_MAX_LATENCY_PS, GG_NLS_LAST_ARRIVAL_PS,
+       GG_NLS_HIST = 8 /* + bit length of latency_ps: 0 for 0, else 64 - clz; 65 bins */,
+       GG_NUM_NLS = GG_NLS_HIST + 65 };
+gg_status gg_noc_latency_stats(const gg_packets* pk, const gg_packet_out* out,
+                               uint64_t* stats /* host, GG_NUM_NLS */, void* stream);
+/* The benchmark in one call: generates the packets of p for cfg.num_tiles
+ * tiles at cfg.frequency_ghz, routes them with gg_noc_route_batch (continuing
+ * from the context's queue state, under any network model the batch API
+ * takes) and reduces the batch to stats.  The packet arrays are scratch of
+ * the context, grown on demand.  Synchronizes the stream.                   */
+gg_status gg_noc_synthetic_run(gg_ctx* ctx, const gg_traffic_params* p, uint64_t* stats, void* stream);
 
 /* Multi-line accesses (replaces the line loop of Core::initiateMemoryAccess,
  * common/tile/core/core.cc:139-266, for the coherent mode).  Input: a
