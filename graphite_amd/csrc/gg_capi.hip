@@ -366,6 +366,13 @@ gg_status gg_noc_get_counters(gg_ctx* ctx, uint64_t* out)
   hipSetDevice(ctx->device);
   GG_HIP(hipStreamSynchronize(ctx->last_stream));
   if (gg_status st = gg_noc_counters(ctx, out)) return st;
+  // the range error of the NoC kernels, in the NoC's words (check_device_errors speaks of trace addresses)
+  uint32_t e = 0;
+  GG_HIP(hipMemcpy(&e, ctx->err_dev, sizeof(e), hipMemcpyDeviceToHost));
+  if (e & GG_DERR_RANGE)
+    return gg_fail(GG_ERR_RANGE, "NoC batch: a packet's source or destination is not a tile id below %u (such packets "
+                   "were left out of every stage), or a port queue's M/G/1 sums left the exactly representable range; "
+                   "the counters are not valid until gg_reset", ctx->cfg.num_tiles);
   return check_device_errors(ctx);
 }
 

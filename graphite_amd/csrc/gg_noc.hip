@@ -608,6 +608,28 @@ __global__ __launch_bounds__(kSweepThreads) void k_chain_sweep(NocDev D, int sta
 // (RegQueue) for the whole chain.  A slab part too large for the LDS batch
 // is cut at a lower time bound (bisection) and served in parts: the order is
 // unchanged.  Chains beyond the limits take the position sweep.
+//
+// Only the steps at which some position serves are executed.  A step at which
+// no position has a pending packet below its slab end serves nothing and hands
+// nothing on: it only moves incoming lists into pools, which the next executed
+// step does as well.  So at the end of a step every position states a lower
+// bound of the next step at which it or the position after it serves: d + 1
+// if it has just handed a packet on, else the first later step at which a
+// packet it holds falls below a slab end, max(d + 1, s + (t - t0) / delta)
+// for the least time t left in its pool; a position not reached yet (d < s)
+// states s if it has start packets.  The block goes on at the minimum of
+// these (s_next).  Every step between is an empty step, by induction from the
+// first of them, whose pending sets are exactly the ones the minimum was
+// taken over; the steps that are executed are those of the plain loop, in its
+// order, with its pending sets, so the argument above holds unchanged.  The
+// incoming lists alternate by executed step (it), not by d, so "written at
+// one step, taken at the next executed one" survives a jump.  An executed
+// step serves a packet or follows one that handed a packet on, so their
+// number is bounded by twice the (packet, position) serves plus the chain's
+// length, whatever the ratio of the drain time to the slab width: a chain
+// whose packets all start at one instant has delta = 1 ps and a drain time of
+// its whole queueing delay, which the plain loop walked picosecond by
+// picosecond into the kMaxSteps backstop.
 // ---------------------------------------------------------------------------
 constexpr uint32_t kPipePos = 32, kPipeK = 2, kPipeWaves = kPipePos / kPipeK, kPipeBatch = 256, kPipePk = 6144;
 // ATAC's ENet gathers a cluster's optical traffic in the access points' columns, twice the packets a mesh
@@ -623,6 +645,15 @@ struct PipePos {
 };
 
 __device__ __forceinline__ bool sk_below(const SK& x, uint64_t bt, uint32_t bi) { return x.t < bt || (x.t == bt && x.i < bi); }
+// the least v of the wave's lanes, as a wave-uniform value (scalar registers)
+__device__ __forceinline__ uint64_t wave_min64n(uint64_t v)
+{
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { const uint64_t u = (uint64_t)__shfl_xor((long long)v, o); v = u < v ? u : v; }
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+  return ((uint64_t)hi << 32) | lo;
+}
 
 __global__ __launch_bounds__(64 * kPipeWaves) void k_chain_pipe(NocDev D, int stage, const uint32_t* __restrict__ dst,
     const uint32_t* __restrict__ len, const uint64_t* __restrict__ bucket_off, uint32_t* __restrict__ bucket_ids,
@@ -645,6 +676,12 @@ __global__ __launch_bounds__(64 * kPipeWaves) void k_chain_pipe(NocDev D, int st
   uint32_t* info = reinterpret_cast<uint32_t*>(A + (size_t)kPipeWaves * kPipeBatch);   // [n] flits | exit position << 16
   uint32_t* npool = info + pk_max;                                             // [npos] pool counts
   uint32_t* ninc = npool + kPipePos;                                           // [2][npos] incoming counts
+  // [3] the next step with a serve, by it % 3 (in kPipeLds' spare words: the static LDS of this kernel and its
+  // fall-backs has no room left beside kStageLdsMax)
+  uint64_t* s_next = reinterpret_cast<uint64_t*>(ninc + 2 * kPipePos);
+  static_assert(((size_t)kPipeWaves * kPipeBatch * sizeof(SK) + (size_t)kPipePkEnet * 4 + 3 * kPipePos * 4) % 8 == 0 &&
+                (size_t)kPipeWaves * kPipeBatch * sizeof(SK) + (size_t)kPipePkEnet * 4 + 3 * kPipePos * 4 + 3 * 8 <= kPipeLds,
+                "s_next in the pipeline's LDS");
   __shared__ uint32_t s_bad, s_left;
   __shared__ uint64_t s_tmin, s_tmax;
   uint32_t* ids = bucket_ids + b;
@@ -656,7 +693,7 @@ __global__ __launch_bounds__(64 * kPipeWaves) void k_chain_pipe(NocDev D, int st
   auto tile_at = [&](uint32_t pos) -> uint32_t { return stage == 0 ? line * P.w + pos : pos * P.w + line; };
   auto sidx = [&](uint32_t pos) { return dir ? pos : npos - 1 - pos; };        // travel index of a position
   auto pos_at = [&](uint32_t s) { return dir ? s : npos - 1 - s; };
-  if (tid == 0) { s_bad = 0; s_left = n; s_tmin = ~0ull; s_tmax = 0; }
+  if (tid == 0) { s_bad = 0; s_left = n; s_tmin = ~0ull; s_tmax = 0; s_next[0] = s_next[1] = s_next[2] = ~0ull; }
   for (uint32_t i = tid; i < kPipePos; i += blockDim.x) { npool[i] = 0; ninc[i] = 0; ninc[kPipePos + i] = 0; }
   __syncthreads();
   // 1. the chain's ids in index order (i = rank by index), info, start pools
@@ -704,20 +741,29 @@ __global__ __launch_bounds__(64 * kPipeWaves) void k_chain_pipe(NocDev D, int st
     }
   }
   SK* mine = A + (size_t)wv * kPipeBatch;
-  constexpr uint64_t kMaxSteps = 1ull << 24;
-  for (uint64_t d = 0;; ++d) {
-    const uint32_t par = (uint32_t)(d & 1);
+  constexpr uint32_t kMaxSteps = 1u << 24;                                      // executed steps (a backstop)
+  uint64_t d = 0;                                                              // the diagonal step
+  for (uint32_t it = 0;; ++it) {                                               // the executed steps, counted
+    const uint32_t par = it & 1u, slot = it % 3u;
+    // s_next[slot] gathers this step's answers and is read after the barrier below; the next step's
+    // slot was last read after the barrier of step it - 2, which every thread has left behind
+    if (tid == 0) s_next[(it + 1u) % 3u] = ~0ull;
 #pragma unroll
     for (uint32_t j = 0; j < kPipeK; ++j) {
       const uint32_t s = wv + j * kPipeWaves;
-      if (s >= npos || d < s) continue;
+      if (s >= npos) continue;
+      if (d < s) {                                                             // not reached yet: its start pool waits for step s
+        if (ln == 0 && npool[s]) atomicMin((unsigned long long*)&s_next[slot], (unsigned long long)s);
+        continue;
+      }
       const uint64_t r = d - s;
+      uint64_t pmin = ~0ull;                 // least time left in the pool (wave-uniform)
       const uint64_t Tr = (r + 1 >= (~0ull - t0) / delta) ? ~0ull : t0 + (r + 1) * delta;   // slab r = [.., Tr)
       // take the incoming packets of the last step into the pool
       SK* pl = pool(s);
       uint32_t np = npool[s];
       {
-        const uint32_t q = par ^ 1u;                                           // the parity written at step d - 1
+        const uint32_t q = par ^ 1u;                                           // the parity written at the last executed step
         uint32_t* cnt = &ninc[q * kPipePos + s];
         const uint32_t k_in = *cnt;
         const SK* src = inc(s, q);
@@ -737,8 +783,11 @@ __global__ __launch_bounds__(64 * kPipeWaves) void k_chain_pipe(NocDev D, int st
           for (uint32_t i = ln; i < np; i += 64) cm += sk_below(pl[i], bt, bi);
           return (uint32_t)wave_sum64n(cm);
         };
-        const uint32_t cntb = count_below(Tr, 0);
-        if (cntb == 0) break;
+        uint32_t cm0 = 0;
+        uint64_t mn = ~0ull;
+        for (uint32_t i = ln; i < np; i += 64) { const SK x = pl[i]; cm0 += sk_below(x, Tr, 0); mn = x.t < mn ? x.t : mn; }
+        const uint32_t cntb = (uint32_t)wave_sum64n(cm0);
+        if (cntb == 0) { pmin = wave_min64n(mn); break; }
         uint64_t bt = Tr;
         uint32_t bi = 0;
         if (cntb > kPipeBatch) {
@@ -759,6 +808,7 @@ __global__ __launch_bounds__(64 * kPipeWaves) void k_chain_pipe(NocDev D, int st
         }
         // split the pool: the part below bound to LDS, the rest compacted in place
         uint32_t m = 0, keep = 0;
+        mn = ~0ull;                                                            // of the packets kept
         for (uint32_t i0 = 0; i0 < np; i0 += 64) {
           const uint32_t i = i0 + ln;
           SK x{~0ull, ~0u, 0};
@@ -769,11 +819,12 @@ __global__ __launch_bounds__(64 * kPipeWaves) void k_chain_pipe(NocDev D, int st
           const uint64_t below = (1ull << ln) - 1;
           if (take) mine[m + __builtin_popcountll(bt & below)] = x;
           nsync();
-          if (kp) pl[keep + __builtin_popcountll(bk & below)] = x;
+          if (kp) { pl[keep + __builtin_popcountll(bk & below)] = x; mn = x.t < mn ? x.t : mn; }
           m += (uint32_t)__builtin_popcountll(bt);
           keep += (uint32_t)__builtin_popcountll(bk);
         }
         np = keep;
+        pmin = wave_min64n(mn);
         uint32_t Mb = 1;
         while (Mb < m) Mb <<= 1;
         for (uint32_t i = m + ln; i < Mb; i += 64) mine[i] = SK{~0ull, ~0u, 0};
@@ -828,10 +879,19 @@ __global__ __launch_bounds__(64 * kPipeWaves) void k_chain_pipe(NocDev D, int st
         if (bt == Tr && bi == 0) break;
       }
       if (ln == 0) npool[s] = np;
+      // the next step with a serve here or at s + 1: the next one if a packet was handed on (only this wave adds
+      // to that list during this step), else the first at which a packet held here is below a slab end
+      uint64_t nxt = ~0ull;
+      if (pmin != ~0ull) nxt = max<uint64_t>(d + 1, s + (pmin - t0) / delta);
+      if (s + 1 < npos && ninc[par * kPipePos + s + 1] != 0) nxt = d + 1;
+      if (ln == 0 && nxt != ~0ull) atomicMin((unsigned long long*)&s_next[slot], (unsigned long long)nxt);
     }
     __syncthreads();
     if (s_left == 0) break;
-    if (d + 1 >= kMaxSteps) { if (tid == 0) atomicOr(D.err, GG_DERR_STATE); break; }
+    const uint64_t nd = s_next[slot];
+    // packets are left but none is pending anywhere, or the backstop: the chain's state is broken
+    if (nd == ~0ull || it + 1 >= kMaxSteps) { if (tid == 0) atomicOr(D.err, GG_DERR_STATE); break; }
+    d = nd;
   }
   // write the queues back, the counters once per position
 #pragma unroll
