@@ -27,7 +27,7 @@ class GGError(RuntimeError):
     def __init__(self, code, msg, statuses=None):
         super().__init__("%s: %s" % (_ERR.get(code, code), msg))
         self.code = code
-        self.statuses = statuses     # coherent_run_many / coherent_advance_many: the status of every instance
+        self.statuses = statuses     # the *_many calls: the status of every instance
 
 
 class LineInfo(ctypes.Structure):
@@ -68,7 +68,8 @@ EXPORTS = ["gg_abi_version", "gg_last_error", "gg_config_default", "gg_create", 
            "gg_coherent_advance", "gg_coherent_snapshot_size", "gg_coherent_snapshot", "gg_coherent_restore",
            "gg_coherent_advance_many",
            "gg_coherent_begin_window", "gg_coherent_next_window", "gg_coherent_window_state",
-           "gg_traffic_params_default", "gg_gen_network_traffic", "gg_noc_latency_stats", "gg_noc_synthetic_run"]
+           "gg_traffic_params_default", "gg_gen_network_traffic", "gg_noc_latency_stats", "gg_noc_synthetic_run",
+           "gg_noc_route_batch_many", "gg_noc_synthetic_run_many"]
 
 # synthetic network traffic (gg_gen_network_traffic): GG_TP_* patterns, GG_NLS_* words of the reduction
 TRAFFIC_PATTERNS = ["uniform_random", "bit_complement", "shuffle", "transpose", "tornado", "nearest_neighbor"]
@@ -215,7 +216,12 @@ def load():
     L.gg_gen_network_traffic.argtypes = [ctypes.POINTER(TrafficParams), u32, ctypes.c_double, vp, vp, vp, vp, vp, vp]
     L.gg_noc_latency_stats.argtypes = [ctypes.POINTER(_Packets), ctypes.POINTER(_PacketOut), vp, vp]
     L.gg_noc_synthetic_run.argtypes = [vp, ctypes.POINTER(TrafficParams), vp, vp]
-    for name in ["gg_gen_network_traffic", "gg_noc_latency_stats", "gg_noc_synthetic_run"]:
+    L.gg_noc_route_batch_many.argtypes = [ctypes.POINTER(vp), u32, ctypes.POINTER(_Packets), ctypes.POINTER(_PacketOut),
+                                          ctypes.POINTER(i32), vp]
+    L.gg_noc_synthetic_run_many.argtypes = [ctypes.POINTER(vp), u32, ctypes.POINTER(TrafficParams), vp,
+                                            ctypes.POINTER(i32), vp]
+    for name in ["gg_gen_network_traffic", "gg_noc_latency_stats", "gg_noc_synthetic_run", "gg_noc_route_batch_many",
+                 "gg_noc_synthetic_run_many"]:
         getattr(L, name).restype = i32
     for name in ["gg_kernel_stats", "gg_shard_map", "gg_coherent_begin", "gg_coherent_quantum", "gg_coherent_export",
                  "gg_coherent_import", "gg_coherent_run", "gg_coherent_get_stats", "gg_gen_hotspot_trace",
@@ -765,6 +771,62 @@ def coherent_advance_many(backends, stops=None, stream=None):
         e.results = results
         raise e
     return results
+
+
+def noc_route_batch_many(backends, batches, outs, stream=None):
+    """Many NoC batches in one set of launches (gg_noc_route_batch_many):
+    backends[i] routes batches[i] = (src, dst, length_bits, time_ps) into
+    outs[i] = (arrival, zero_load, contention), exactly as its
+    noc_route_batch would.  The backends must be launch-compatible
+    (include/graphite_gpu.h).  Returns the list of per-instance statuses; if
+    any is non-zero raises GGError carrying that list (e.statuses) — the other
+    instances have been routed."""
+    import torch
+    n = len(backends)
+    if not (len(batches) == len(outs) == n):
+        raise ValueError("one batch and one output triple per backend")
+    pks = (_Packets * max(n, 1))()
+    pos = (_PacketOut * max(n, 1))()
+    for i in range(n):
+        src, dst, length_bits, time_ps = batches[i]
+        arrival, zero_load, contention = outs[i]
+        m = src.numel()
+        for t, dt in ((src, torch.int32), (dst, torch.int32), (length_bits, torch.int32), (time_ps, torch.int64),
+                      (arrival, torch.int64), (zero_load, torch.int64), (contention, torch.int64)):
+            _need_dev(t, dt, m)
+        pks[i] = _Packets(src.data_ptr(), dst.data_ptr(), length_bits.data_ptr(), time_ps.data_ptr(), m)
+        pos[i] = _PacketOut(arrival.data_ptr(), zero_load.data_ptr(), contention.data_ptr())
+    hs = (ctypes.c_void_p * max(n, 1))(*[be.h for be in backends])
+    st = (ctypes.c_int * max(n, 1))()
+    rc = load().gg_noc_route_batch_many(hs, n, pks, pos, st, _stream(stream))
+    statuses = [int(st[i]) for i in range(n)]
+    if rc != GG_OK:
+        raise GGError(rc, load().gg_last_error().decode(errors="replace"), statuses)
+    return statuses
+
+
+def noc_synthetic_run_many(backends, params, stream=None):
+    """gg_noc_synthetic_run_many: backends[i] generates, routes and reduces
+    params[i] (TrafficParams) as its noc_synthetic_run would, all instances in
+    one set of launches.  Returns the [n][NUM_NLS] words; if an instance fails
+    raises GGError carrying the per-instance statuses (e.statuses) and that
+    array (e.stats; the rows of failed instances are zero) — the other
+    instances have run."""
+    n = len(backends)
+    if len(params) != n:
+        raise ValueError("one TrafficParams per backend")
+    ps = (TrafficParams * max(n, 1))()
+    for i, p in enumerate(params):
+        ps[i] = p
+    stats = np.zeros((n, NUM_NLS), np.uint64)
+    hs = (ctypes.c_void_p * max(n, 1))(*[be.h for be in backends])
+    st = (ctypes.c_int * max(n, 1))()
+    rc = load().gg_noc_synthetic_run_many(hs, n, ps, stats.ctypes.data_as(ctypes.c_void_p), st, _stream(stream))
+    if rc != GG_OK:
+        e = GGError(rc, load().gg_last_error().decode(errors="replace"), [int(st[i]) for i in range(n)])
+        e.stats = stats
+        raise e
+    return stats
 
 
 def shard_map(num_tiles, num_shards):

@@ -13,8 +13,16 @@
 // destination — so each stage runs its chains independently, one thread per
 // chain with a private (time, index) event heap, which reproduces the order of
 // one global event queue exactly.
+//
+// Layout.  The first part holds the device bodies of the batch kernels, the
+// second (behind GG_NOC_DEVICE_ONLY) the kernels that wrap them, the broadcast
+// tree and the host side.  gg_noc_many.hip (many batches side by side,
+// DESIGN.md §4l) includes this file for the first part alone and wraps the
+// same bodies, fed from an instance record instead of launch arguments, so the
+// two forms cannot diverge.
 #include "gg_dev.h"
 #include "gg_noc_stage.h"
+#include "gg_noc_many.h"
 
 #include <hip/hip_cooperative_groups.h>
 
@@ -32,13 +40,12 @@ using namespace gg;
 enum { P_SELF = 0, P_LEFT, P_RIGHT, P_DOWN, P_UP, NPORTS };   // network_model_emesh_hop_by_hop.h:41-48
 
 // ---------------------------------------------------------------------------
-// hop counter / magic: one thread per packet
+// hop counter / magic: one thread per packet (k = the packet)
 // ---------------------------------------------------------------------------
-__global__ void k_hop_counter(NocParams P, const uint32_t* __restrict__ src, const uint32_t* __restrict__ dst,
-                              const uint32_t* __restrict__ len, const uint64_t* __restrict__ t0, uint64_t n,
-                              uint64_t* arrival, uint64_t* zero_load, uint64_t* contention, uint64_t* ctr)
+__device__ __forceinline__ void hop_counter_body(const NocParams& P, const uint32_t* __restrict__ src,
+    const uint32_t* __restrict__ dst, const uint32_t* __restrict__ len, const uint64_t* __restrict__ t0, uint64_t n,
+    uint64_t* arrival, uint64_t* zero_load, uint64_t* contention, uint64_t* ctr, uint64_t k)
 {
-  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n) return;
   uint64_t zl = 0;
   arrival[k] = route_closed_form(P, src[k], dst[k], len[k], t0[k], zl, ctr);
@@ -237,11 +244,10 @@ __device__ void inject_tile(const NocDev& D, uint32_t tile, const uint32_t* __re
 // Stages X and Y, chains whose queue images do not fit LDS (large
 // max_list_size): one thread per chain, ports along the chain in (time,
 // index) order, queues in HBM.
-__global__ void k_chain(NocDev D, int stage, const uint32_t* __restrict__ src, const uint32_t* __restrict__ dst,
+__device__ __forceinline__ void chain_hbm(const NocDev& D, int stage, const uint32_t* __restrict__ dst,
                         const uint32_t* __restrict__ len, const uint64_t* __restrict__ bucket_off,
-                        const uint32_t* __restrict__ bucket_ids, Ev* heap, PktState S, uint32_t nchains)
+                        const uint32_t* __restrict__ bucket_ids, Ev* heap, const PktState& S, uint32_t nchains, uint32_t c)
 {
-  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= nchains) return;
   const NocParams& P = D.P;
   const uint64_t b = bucket_off[c], e = bucket_off[c + 1];
@@ -583,14 +589,6 @@ __device__ void chain_sweep(NocDev D, int stage, const uint32_t* __restrict__ ds
     atomicMax(&prof[8 * stage + 6], (unsigned long long)(__builtin_amdgcn_s_memtime() - c_0));
   }
 }
-__global__ __launch_bounds__(kSweepThreads) void k_chain_sweep(NocDev D, int stage, const uint32_t* __restrict__ dst,
-    const uint32_t* __restrict__ len, const uint64_t* __restrict__ bucket_off, uint32_t* __restrict__ bucket_ids,
-    Ev* heap, PktState S, unsigned long long* prof)
-{
-  if (!GG_NOC_DIAG) prof = nullptr;
-  chain_sweep(D, stage, dst, len, bucket_off, bucket_ids, heap, S, prof, blockIdx.x);
-}
-
 // ---------------------------------------------------------------------------
 // Stages X / Y as a pipeline of time slabs (the default for chains of <=
 // kPipePos positions): the positions of a chain serve concurrently, one wave
@@ -655,14 +653,14 @@ __device__ __forceinline__ uint64_t wave_min64n(uint64_t v)
   return ((uint64_t)hi << 32) | lo;
 }
 
-__global__ __launch_bounds__(64 * kPipeWaves) void k_chain_pipe(NocDev D, int stage, const uint32_t* __restrict__ dst,
+// c: the chain (the block's index in its instance's grid); 64 * kPipeWaves threads
+__device__ __forceinline__ void chain_pipe(const NocDev& D, int stage, const uint32_t* __restrict__ dst,
     const uint32_t* __restrict__ len, const uint64_t* __restrict__ bucket_off, uint32_t* __restrict__ bucket_ids,
-    Ev* heap, PktState S, SK* pscr, uint64_t pstride, uint32_t pk_max, unsigned long long* prof)
+    Ev* heap, const PktState& S, SK* pscr, uint64_t pstride, uint32_t pk_max, unsigned long long* prof, uint32_t c)
 {
-  if (!GG_NOC_DIAG) prof = nullptr;
   extern __shared__ __attribute__((aligned(16))) uint8_t qlds[];
   const NocParams& P = D.P;
-  const uint32_t c = blockIdx.x, line = c / 2, dir = c % 2, tid = threadIdx.x, ln = tid & 63, wv = tid >> 6;
+  const uint32_t line = c / 2, dir = c % 2, tid = threadIdx.x, ln = tid & 63, wv = tid >> 6;
   const uint64_t b = bucket_off[c], e = bucket_off[c + 1];
   if (b == e) return;
   const uint32_t npos = stage == 0 ? P.w : P.h;
@@ -922,14 +920,16 @@ __global__ __launch_bounds__(64 * kPipeWaves) void k_chain_pipe(NocDev D, int st
 constexpr uint32_t kPortWaves = 4, kPortPk = 2048;
 constexpr size_t kPortLds = (size_t)kPortWaves * kPortPk * sizeof(SK);
 
+// blk: the block's index in its instance's grid; 64 * kPortWaves threads
 template <bool SELF>
-__global__ __launch_bounds__(64 * kPortWaves) void k_port_sweep(NocDev D, const uint32_t* __restrict__ len,
-    const uint64_t* __restrict__ bucket_off, const uint32_t* __restrict__ bucket_ids, Ev* heap, PktState S)
+__device__ __forceinline__ void port_sweep(const NocDev& D, const uint32_t* __restrict__ len,
+    const uint64_t* __restrict__ bucket_off, const uint32_t* __restrict__ bucket_ids, Ev* heap, const PktState& S,
+    uint32_t blk)
 {
   extern __shared__ __attribute__((aligned(16))) uint8_t qlds[];
   const NocParams& P = D.P;
   const uint32_t ln = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const uint32_t tile = blockIdx.x * kPortWaves + wv;
+  const uint32_t tile = blk * kPortWaves + wv;
   if (tile >= P.tiles) return;
   const uint64_t b = bucket_off[tile], e = bucket_off[tile + 1];
   if (b == e) return;
@@ -1018,11 +1018,11 @@ __global__ __launch_bounds__(64 * kPortWaves) void k_port_sweep(NocDev D, const 
 
 // bucket keys: 0 = injection (src tile), 1 = X chain, 2 = Y chain, 3 = SELF (dst tile); ~0 = not in stage
 
-__global__ void k_keys(NocParams P, int stage, const uint32_t* __restrict__ src, const uint32_t* __restrict__ dst,
-                       uint64_t cap, const uint32_t* n_dev, uint32_t* keys, uint32_t* counts, uint32_t* err)
+__device__ __forceinline__ void keys_body(const NocParams& P, int stage, const uint32_t* __restrict__ src,
+                       const uint32_t* __restrict__ dst, uint64_t cap, const uint32_t* n_dev, uint32_t* keys,
+                       uint32_t* counts, uint32_t* err, uint64_t k)
 {
   const uint64_t n = batch_n(cap, n_dev);
-  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n) return;
   const uint32_t s = src[k], d = dst[k];
   if (s >= P.tiles || d >= P.tiles) { atomicOr(err, GG_DERR_RANGE); keys[k] = ~0u; return; }
@@ -1038,13 +1038,94 @@ __global__ void k_keys(NocParams P, int stage, const uint32_t* __restrict__ src,
 }
 
 
+__device__ __forceinline__ void init_pkts_body(const uint32_t* __restrict__ src, const uint64_t* __restrict__ t0,
+                                               uint64_t cap, const uint32_t* n_dev, const PktState& S, uint64_t k)
+{
+  const uint64_t n = batch_n(cap, n_dev);
+  if (k >= n) return;
+  S.t[k] = t0[k]; S.zl[k] = 0; S.ct[k] = 0; S.cur[k] = src[k];
+}
+
+// The stage-kernel form of the X (stage 1) or Y (stage 2) chains, from the
+// derived parameters alone: what noc_hbh_stages launches, and what an ensemble
+// (gg_noc_route_batch_many) needs alike in all its contexts.
+enum { NOC_FORM_PIPE = 0, NOC_FORM_SWEEP, NOC_FORM_HBM };
+inline int noc_stage_form(const NocParams& P, int stage)
+{
+  // the general walk (chain_staged, the fallback of the pipeline and the sweep) stages the chain's
+  // queue images in LDS
+  const size_t chain_lds = (size_t)(stage == 1 ? P.w : P.h) * qimg_bytes(P.max_size);
+  if (chain_lds > kStageLdsMax) return NOC_FORM_HBM;
+  return (P.w > P.h ? P.w : P.h) <= kPipePos ? NOC_FORM_PIPE : NOC_FORM_SWEEP;
+}
+
+// One instance of an ensemble launch (gg_noc_many.hip): what the single
+// launches of gg_noc_run / noc_hbh_stages pass by value, in a device table the
+// block indexes by blockIdx.y.  Written by the host before the launches and
+// constant for all of them.
+struct NocManyRec {
+  NocDev D;
+  PktState S;
+  const uint32_t* src; const uint32_t* dst; const uint32_t* len; const uint64_t* t0;
+  uint64_t n;                                     // packets (> 0)
+  uint64_t* arrival; uint64_t* zero_load; uint64_t* contention;
+  uint64_t* off; uint32_t* ids; uint32_t* keys; uint32_t* counts; uint32_t* cursor;
+  Ev* heap;
+  SK* pscr; uint64_t pstride; uint32_t pk_max;    // the slab pipeline's pool, its stride and packet cap
+  // gg_noc_synthetic_run_many: the generator's stop word.  Non-zero: the instance's packets are not
+  // all written, and every routing block of the instance returns at once.  NULL for a plain batch.
+  const uint32_t* stop;
+};
+
+}  // namespace
+
+#ifndef GG_NOC_DEVICE_ONLY
+namespace {
+using namespace gg;
+
+// The batch kernels: the bodies above on this launch's arguments.
+__global__ void k_hop_counter(NocParams P, const uint32_t* __restrict__ src, const uint32_t* __restrict__ dst,
+                              const uint32_t* __restrict__ len, const uint64_t* __restrict__ t0, uint64_t n,
+                              uint64_t* arrival, uint64_t* zero_load, uint64_t* contention, uint64_t* ctr)
+{
+  hop_counter_body(P, src, dst, len, t0, n, arrival, zero_load, contention, ctr,
+                   (uint64_t)blockIdx.x * blockDim.x + threadIdx.x);
+}
+__global__ void k_chain(NocDev D, int stage, const uint32_t* __restrict__ src, const uint32_t* __restrict__ dst,
+                        const uint32_t* __restrict__ len, const uint64_t* __restrict__ bucket_off,
+                        const uint32_t* __restrict__ bucket_ids, Ev* heap, PktState S, uint32_t nchains)
+{
+  chain_hbm(D, stage, dst, len, bucket_off, bucket_ids, heap, S, nchains, blockIdx.x * blockDim.x + threadIdx.x);
+}
+__global__ __launch_bounds__(kSweepThreads) void k_chain_sweep(NocDev D, int stage, const uint32_t* __restrict__ dst,
+    const uint32_t* __restrict__ len, const uint64_t* __restrict__ bucket_off, uint32_t* __restrict__ bucket_ids,
+    Ev* heap, PktState S, unsigned long long* prof)
+{
+  if (!GG_NOC_DIAG) prof = nullptr;
+  chain_sweep(D, stage, dst, len, bucket_off, bucket_ids, heap, S, prof, blockIdx.x);
+}
+__global__ __launch_bounds__(64 * kPipeWaves) void k_chain_pipe(NocDev D, int stage, const uint32_t* __restrict__ dst,
+    const uint32_t* __restrict__ len, const uint64_t* __restrict__ bucket_off, uint32_t* __restrict__ bucket_ids,
+    Ev* heap, PktState S, SK* pscr, uint64_t pstride, uint32_t pk_max, unsigned long long* prof)
+{
+  if (!GG_NOC_DIAG) prof = nullptr;
+  chain_pipe(D, stage, dst, len, bucket_off, bucket_ids, heap, S, pscr, pstride, pk_max, prof, blockIdx.x);
+}
+template <bool SELF>
+__global__ __launch_bounds__(64 * kPortWaves) void k_port_sweep(NocDev D, const uint32_t* __restrict__ len,
+    const uint64_t* __restrict__ bucket_off, const uint32_t* __restrict__ bucket_ids, Ev* heap, PktState S)
+{
+  port_sweep<SELF>(D, len, bucket_off, bucket_ids, heap, S, blockIdx.x);
+}
+__global__ void k_keys(NocParams P, int stage, const uint32_t* __restrict__ src, const uint32_t* __restrict__ dst,
+                       uint64_t cap, const uint32_t* n_dev, uint32_t* keys, uint32_t* counts, uint32_t* err)
+{
+  keys_body(P, stage, src, dst, cap, n_dev, keys, counts, err, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x);
+}
 __global__ void k_init_pkts(const uint32_t* __restrict__ src, const uint64_t* __restrict__ t0, uint64_t cap,
                             const uint32_t* n_dev, PktState S)
 {
-  const uint64_t n = batch_n(cap, n_dev);
-  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= n) return;
-  S.t[k] = t0[k]; S.zl[k] = 0; S.ct[k] = 0; S.cur[k] = src[k];
+  init_pkts_body(src, t0, cap, n_dev, S, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 __global__ void k_htree_reset(HQueue* q, HNode* nd, uint64_t nq, uint32_t max_size, uint32_t type, uint32_t aux)
@@ -2075,6 +2156,7 @@ struct gg_noc_state {
   gg_dbuf<SK> pscr;                               // k_chain_pipe: per packet 3 x positions pool / incoming slots
   gg_dbuf<uint8_t> tp;                            // k_tree_pool: TpBufs
   gg_dbuf<uint8_t> tg;                            // k_tree_setup / k_tree_grid: TgBufs
+  gg_dbuf<uint8_t> many_tab;                      // gg_noc_route_batch_many with this context first: the instance table
 };
 
 gg_status gg_noc_alloc(gg_ctx* ctx)
@@ -2147,16 +2229,23 @@ static gg_status noc_grow(gg_noc_state* S, uint64_t n, uint32_t nb)
   return gg_reserve_all((uint64_t)nb + 1, (uint64_t)nb + 1, S->counts, S->cursor, S->off);
 }
 
+// a non-empty batch's own arguments (gg_noc_run, gg_noc_many_prepare)
+static gg_status noc_batch_check(const gg_packets* pk, const gg_packet_out* out)
+{
+  if (!pk->src_dev || !pk->dst_dev || !pk->length_bits_dev || !pk->time_ps_dev ||
+      !out->arrival_ps_dev || !out->zero_load_ps_dev || !out->contention_ps_dev)
+    return gg_fail(GG_ERR_INVALID, "NULL packet or output pointer");
+  if (pk->num_packets >= (1ull << 32)) return gg_fail(GG_ERR_RANGE, "batch larger than 2^32 packets");
+  return GG_OK;
+}
+
 gg_status gg_noc_run(gg_ctx* ctx, const gg_packets* pk, const gg_packet_out* out, hipStream_t s)
 {
   gg_noc_state* S = ctx->noc;
   const NocParams& P = S->P;
   const uint64_t n = pk->num_packets;
   if (n == 0) return GG_OK;
-  if (!pk->src_dev || !pk->dst_dev || !pk->length_bits_dev || !pk->time_ps_dev ||
-      !out->arrival_ps_dev || !out->zero_load_ps_dev || !out->contention_ps_dev)
-    return gg_fail(GG_ERR_INVALID, "NULL packet or output pointer");
-  if (n >= (1ull << 32)) return gg_fail(GG_ERR_RANGE, "batch larger than 2^32 packets");
+  if (gg_status st = noc_batch_check(pk, out)) return st;
   const uint32_t blocks = (uint32_t)((n + 255) / 256);
   if (P.net_model == GG_NET_MAGIC || P.net_model == GG_NET_EMESH_HOP_COUNTER) {
     gg_timer_begin(ctx, "noc_hop_counter", s);
@@ -2355,11 +2444,7 @@ static gg_status noc_hbh_stages(gg_ctx* ctx, const uint32_t* src, const uint32_t
     hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, s, S->counts, nb, S->off, S->cursor);
     hipLaunchKernelGGL(k_bucket, dim3(blocks), dim3(256), 0, s, S->keys, cap, n_dev, S->off, S->cursor, S->ids);
     const uint32_t tb = (nb + 63) / 64;
-    const size_t qb = qimg_bytes(P.max_size);
-    // chains: the general walk (chain_staged, the fallback of the pipeline and the sweep) stages the
-    // chain's queue images in LDS
-    const size_t chain_lds = (stage == 1 ? P.w : P.h) * qb;
-    const bool staged = chain_lds <= kStageLdsMax;
+    const int form = noc_stage_form(P, stage);
     if (stage == 0 || stage == 3) {
       const uint32_t pb = (P.tiles + kPortWaves - 1) / kPortWaves;
       if (stage == 0)
@@ -2368,12 +2453,12 @@ static gg_status noc_hbh_stages(gg_ctx* ctx, const uint32_t* src, const uint32_t
       else
         hipLaunchKernelGGL(k_port_sweep<true>, dim3(pb), dim3(64 * kPortWaves), kPortLds, s, D, len, S->off, S->ids,
                            S->heap, PS);
-    } else if (staged && std::max(P.w, P.h) <= kPipePos) {
+    } else if (form == NOC_FORM_PIPE) {
       const uint64_t stride = 3ull * std::max(P.w, P.h);
       if (gg_status st = S->pscr.reserve(cap * stride)) return st;
       hipLaunchKernelGGL(k_chain_pipe, dim3(nb), dim3(64 * kPipeWaves), kStageLdsMax, s, D, stage - 1, dst, len, S->off,
                          S->ids, S->heap, PS, S->pscr, stride, P.net_model == GG_NET_ATAC ? kPipePkEnet : kPipePk, S->prof);
-    } else if (staged) {
+    } else if (form == NOC_FORM_SWEEP) {
       hipLaunchKernelGGL(k_chain_sweep, dim3(nb), dim3(kSweepThreads), kStageLdsMax, s, D, stage - 1, dst, len, S->off,
                          S->ids, S->heap, PS, S->prof);
     } else {
@@ -2397,6 +2482,40 @@ static gg_status noc_hbh_stages(gg_ctx* ctx, const uint32_t* src, const uint32_t
 }
 
 const uint64_t* gg_noc_packet_times(gg_ctx* ctx) { return ctx->noc->t; }
+
+// ---- gg_noc_route_batch_many (gg_noc_many.hip): this context as one instance
+int gg_noc_form(gg_ctx* ctx, int stage) { return noc_stage_form(ctx->noc->P, stage); }
+
+gg_status gg_noc_many_table(gg_ctx* ctx, uint64_t bytes, void** dev)
+{
+  if (gg_status st = ctx->noc->many_tab.reserve(bytes)) return st;
+  *dev = ctx->noc->many_tab.get();
+  return GG_OK;
+}
+
+gg_status gg_noc_many_prepare(gg_ctx* ctx, const gg_packets* pk, const gg_packet_out* out, gg_noc_view* v)
+{
+  gg_noc_state* S = ctx->noc;
+  const NocParams& P = S->P;
+  if (gg_status st = noc_batch_check(pk, out)) return st;
+  const uint64_t n = pk->num_packets;
+  *v = gg_noc_view{};
+  v->P = P; v->q = S->q; v->nd = S->nd; v->ctr = S->ctr;
+  if (P.net_model == GG_NET_MAGIC || P.net_model == GG_NET_EMESH_HOP_COUNTER) return GG_OK;
+  if (P.net_model != GG_NET_EMESH_HOP_BY_HOP) return gg_fail(GG_ERR_UNSUPPORTED, "network model %u", P.net_model);
+  if (P.w * P.h != P.tiles) return gg_fail(GG_ERR_UNSUPPORTED, "emesh_hop_by_hop needs a full W x H mesh (hop_by_hop.cc:55-59)");
+  const uint32_t nb_max = std::max(P.tiles, 2 * std::max(P.w, P.h));
+  if (gg_status st = noc_grow(S, n, nb_max)) return st;
+  if (noc_stage_form(P, 1) == NOC_FORM_PIPE || noc_stage_form(P, 2) == NOC_FORM_PIPE) {
+    v->pstride = 3ull * std::max(P.w, P.h);
+    if (gg_status st = S->pscr.reserve(n * v->pstride)) return st;
+    v->pscr = S->pscr.get();
+    v->pk_max = kPipePk;
+  }
+  v->t = S->t; v->zl = S->zl; v->ct = S->ct; v->cur = S->cur; v->keys = S->keys; v->ids = S->ids;
+  v->heap = S->heap.get(); v->counts = S->counts; v->cursor = S->cursor; v->off = S->off;
+  return GG_OK;
+}
 
 gg_status gg_noc_counters(gg_ctx* ctx, uint64_t* out)
 {
@@ -2443,3 +2562,4 @@ void gg_noc_packet_state(gg_ctx* ctx, uint64_t** t, uint64_t** zl, uint64_t** ct
 }
 // ATAC: the mesh stages are the ENet (its router delay; the ENet link is 1 cycle)
 void gg_noc_set_enet(gg_ctx* ctx, uint32_t router_delay) { ctx->noc->P.router_delay = router_delay; ctx->noc->P.link_delay = 1; }
+#endif  // GG_NOC_DEVICE_ONLY

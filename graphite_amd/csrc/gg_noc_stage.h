@@ -44,7 +44,8 @@ __device__ void block_bitonic(T* a, uint32_t M, Lt lt)
 
 __device__ __forceinline__ uint64_t batch_n(uint64_t n, const uint32_t* n_dev) { return n_dev ? min((uint64_t)*n_dev, n) : n; }
 
-__global__ void k_scan_counts(const uint32_t* counts, uint32_t nb, uint64_t* off, uint32_t* cursor)
+// (the bodies are shared with the ensemble launches of gg_noc_many.hip)
+__device__ __forceinline__ void scan_counts_body(const uint32_t* counts, uint32_t nb, uint64_t* off, uint32_t* cursor)
 {
   // single block; nb is small (<= 2 * 4096)
   __shared__ uint64_t part[1024];
@@ -58,16 +59,24 @@ __global__ void k_scan_counts(const uint32_t* counts, uint32_t nb, uint64_t* off
   uint64_t a = part[t];
   for (uint32_t i = t * per; i < min(nb, (t + 1) * per); ++i) { off[i] = a; cursor[i] = 0; a += counts[i]; }
 }
+__global__ void k_scan_counts(const uint32_t* counts, uint32_t nb, uint64_t* off, uint32_t* cursor)
+{
+  scan_counts_body(counts, nb, off, cursor);
+}
 
-__global__ void k_bucket(const uint32_t* __restrict__ keys, uint64_t cap, const uint32_t* n_dev,
-                         const uint64_t* __restrict__ off, uint32_t* cursor, uint32_t* ids)
+__device__ __forceinline__ void bucket_body(const uint32_t* __restrict__ keys, uint64_t cap, const uint32_t* n_dev,
+                                            const uint64_t* __restrict__ off, uint32_t* cursor, uint32_t* ids, uint64_t k)
 {
   const uint64_t n = batch_n(cap, n_dev);
-  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n) return;
   const uint32_t key = keys[k];
   if (key == ~0u) return;
   ids[off[key] + atomicAdd(&cursor[key], 1u)] = (uint32_t)k;
+}
+__global__ void k_bucket(const uint32_t* __restrict__ keys, uint64_t cap, const uint32_t* n_dev,
+                         const uint64_t* __restrict__ off, uint32_t* cursor, uint32_t* ids)
+{
+  bucket_body(keys, cap, n_dev, off, cursor, ids, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 }  // namespace

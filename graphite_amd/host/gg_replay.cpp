@@ -54,7 +54,10 @@
 //       the reference's NoC benchmark (synthetic_network.cc -p PATTERN -l L -s S
 //       -N N) generated, routed and reduced on the device (gg_noc_synthetic_run):
 //       the network summaries as --route prints them, then one line of the
-//       reduction (packets, mean / max latency, mean contention, last arrival)
+//       reduction (packets, mean / max latency, mean contention, last arrival).
+//       --load takes a comma-separated list: one such block per load, each on
+//       a context of its own; unless M is atac the list runs in one
+//       gg_noc_synthetic_run_many call
 //   gg_replay --summary-selftest
 //       prints writeCacheSummary() for fixed counters (no GPU needed)
 //   gg_replay --mosi-summary FILE TILES
@@ -72,6 +75,7 @@
 #include <sstream>
 #include <string>
 #include <thread>
+#include <memory>
 #include <vector>
 
 #include "graphite_host.hpp"
@@ -100,6 +104,7 @@ int main(int argc, char** argv)
   uint32_t shards = 1;
   std::string synth_pattern;
   gg_traffic_params synth;
+  std::vector<double> synth_loads;       // --load: one offered load per point
   gg_traffic_params_default(&synth);
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -179,7 +184,15 @@ int main(int argc, char** argv)
       return 0;
     }
     else if (a == "--synthetic-network") synth_pattern = next();
-    else if (a == "--load") synth.offered_load = std::strtod(next(), nullptr);
+    else if (a == "--load") {
+      synth_loads.clear();
+      for (const char* q = next();;) {
+        char* e = nullptr;
+        synth_loads.push_back(std::strtod(q, &e));
+        if (*e != ',') break;
+        q = e + 1;
+      }
+    }
     else if (a == "--packet-bytes") synth.packet_bytes = (uint32_t)std::strtoul(next(), nullptr, 0);
     else if (a == "--packets") synth.packets_per_tile = std::strtoull(next(), nullptr, 0);
     else if (a == "--seed") synth.seed = std::strtoull(next(), nullptr, 0);
@@ -260,14 +273,34 @@ int main(int argc, char** argv)
       gg_config cfg;
       gg_config_default(&cfg, tiles);
       cfg.net_model = net;
-      Backend be(cfg);
-      const std::vector<uint64_t> stats = SyntheticNetwork(be).run(synth);
-      std::vector<uint64_t> nc((size_t)tiles * GG_NUM_NET_COUNTERS);
-      check(gg_noc_get_counters(be.ctx(), nc.data()), "gg_noc_get_counters");
-      for (uint32_t t = 0; t < tiles; ++t)
-        writeNetworkSummary(std::cout, &nc[(size_t)t * GG_NUM_NET_COUNTERS], cfg.frequency_ghz, cfg.net_model,
-                            cfg.net_model == GG_NET_EMESH_HOP_BY_HOP);
-      writeLatencyStats(std::cout, stats.data());
+      if (synth_loads.empty()) synth_loads.push_back(synth.offered_load);
+      const size_t np = synth_loads.size();
+      std::vector<std::unique_ptr<Backend>> bes;
+      std::vector<gg_traffic_params> params(np, synth);
+      for (size_t i = 0; i < np; ++i) {
+        bes.emplace_back(new Backend(cfg));
+        params[i].offered_load = synth_loads[i];
+      }
+      std::vector<uint64_t> stats(np * GG_NUM_NLS);
+      if (net == GG_NET_ATAC) {
+        for (size_t i = 0; i < np; ++i) {
+          const std::vector<uint64_t> s = SyntheticNetwork(*bes[i]).run(params[i]);
+          std::copy(s.begin(), s.end(), stats.begin() + i * GG_NUM_NLS);
+        }
+      } else {
+        std::vector<gg_ctx*> ctxs;
+        for (auto& b : bes) ctxs.push_back(b->ctx());
+        check(gg_noc_synthetic_run_many(ctxs.data(), (uint32_t)np, params.data(), stats.data(), nullptr, nullptr),
+              "gg_noc_synthetic_run_many");
+      }
+      for (size_t i = 0; i < np; ++i) {
+        std::vector<uint64_t> nc((size_t)tiles * GG_NUM_NET_COUNTERS);
+        check(gg_noc_get_counters(bes[i]->ctx(), nc.data()), "gg_noc_get_counters");
+        for (uint32_t t = 0; t < tiles; ++t)
+          writeNetworkSummary(std::cout, &nc[(size_t)t * GG_NUM_NET_COUNTERS], cfg.frequency_ghz, cfg.net_model,
+                              cfg.net_model == GG_NET_EMESH_HOP_BY_HOP);
+        writeLatencyStats(std::cout, &stats[i * GG_NUM_NLS]);
+      }
     } catch (const std::exception& e) {
       std::fprintf(stderr, "gg_replay: %s\n", e.what());
       return 1;

@@ -42,6 +42,8 @@
  *                              tests/benchmarks/synthetic_network/synthetic_network.cc:140-359
  *   gg_noc_latency_stats       its result: packets, latency and contention of a batch
  *   gg_noc_synthetic_run       the benchmark in one call on a context
+ *   gg_noc_route_batch_many    many independent batches, each on its own context,
+ *   gg_noc_synthetic_run_many  in one set of launches (a load-latency sweep)
  *
  * Conventions: every function returns a gg_status (0 = OK, negative = error);
  * no exception crosses the ABI; pointers named *_dev are HIP device pointers,
@@ -1027,6 +1029,58 @@ gg_status gg_noc_latency_stats(const gg_packets* pk, const gg_packet_out* out,
  * takes) and reduces the batch to stats.  The packet arrays are scratch of
  * the context, grown on demand.  Synchronizes the stream.                   */
 gg_status gg_noc_synthetic_run(gg_ctx* ctx, const gg_traffic_params* p, uint64_t* stats, void* stream);
+
+/* Many NoC batches side by side: a load-latency sweep is a
+ * set of independent batches on independent contexts.  Instance i does what
+ * gg_noc_route_batch(ctxs[i], &pks[i], &outs[i], stream) does, bit for bit —
+ * the three output arrays, the context's NoC counters, the port-queue state a
+ * later batch (single or _many) continues from, the deferred GG_ERR_RANGE of
+ * gg_noc_get_counters for a packet naming no tile — but all instances share
+ * one set of launches on stream (grid y = instance), about two dozen enqueues
+ * for the whole set, with no host synchronisation.  Each instance uses the
+ * state and scratch of its own context.  Not synchronised: as the single call.
+ * Network models: emesh_hop_by_hop (with or without the queue model, any
+ * queue-model type), emesh_hop_counter, magic.  An ATAC context:
+ * GG_ERR_UNSUPPORTED for the whole call, naming the index.
+ * Launch-compatible contexts.  The contexts must share the device, num_tiles
+ * (hence the mesh w x h) and the network model, and under emesh_hop_by_hop the
+ * stage-kernel form derived from the configuration, per X and Y stage: the
+ * slab pipeline (max(w, h) <= 32), the position sweep, or the chain walk with
+ * queues in HBM (side x queue image of max_list_size beyond the LDS budget).
+ * The rule is applied to the derived state, not to config fields: everything
+ * else may differ — the batch and its length, frequency_ghz, router_delay,
+ * link_delay, flit_width, queue_model_enabled, the queue-model type and its
+ * parameter, and max_list_size as long as the form stays the same.  The
+ * fall-backs a stage kernel takes per chain or port (a long chain, a packet
+ * of 2^16 flits or more, a non-tree queue model) depend on traffic and stay
+ * per-instance decisions inside the kernel.
+ * GG_ERR_INVALID (GG_ERR_UNSUPPORTED for ATAC), with gg_last_error naming the
+ * first offending index and field, for: n == 0, n > GG_MANY_MAX, a NULL array
+ * argument, a NULL or repeated context, an incompatible context (compared with
+ * context 0), an ATAC context — before any launch and any change of a
+ * context's state.  What gg_noc_route_batch would return for one instance's
+ * own batch (a NULL packet or output pointer with num_packets > 0, 2^32
+ * packets or more, a failed allocation) fails that instance alone, with that
+ * status in statuses[i] (may be NULL); the others run.  num_packets == 0 is
+ * GG_OK and leaves the context untouched.  Returns the first non-zero status,
+ * or GG_OK.  Launches are not timed per kernel: the "noc_route_many" timer of
+ * gg_set_timing covers the call on ctxs[0].                                  */
+gg_status gg_noc_route_batch_many(gg_ctx* const* ctxs, uint32_t n, const gg_packets* pks, const gg_packet_out* outs,
+                                  gg_status* statuses /* may be NULL */, void* stream);
+/* gg_noc_synthetic_run for a set: instance i equals gg_noc_synthetic_run(
+ * ctxs[i], &params[i], stats + i * GG_NUM_NLS, stream) — the same packets and
+ * routed results in the context's scratch arrays, the same 73 words.  One
+ * generator launch over (instance, tile), the routing of
+ * gg_noc_route_batch_many, one reduction launch over the instances, one
+ * device-to-host copy and one synchronisation for the whole call.  The
+ * parameters of instance i are checked as gg_noc_synthetic_run checks them,
+ * before any launch; a failure is that instance's status and the others run.
+ * A generator that stops at cycle 2^32 - 64 is that instance's GG_ERR_RANGE
+ * (it is not routed).  stats of a failed instance are not written.  Set-level
+ * rejections as gg_noc_route_batch_many.                                     */
+gg_status gg_noc_synthetic_run_many(gg_ctx* const* ctxs, uint32_t n, const gg_traffic_params* params,
+                                    uint64_t* stats /* host, n * GG_NUM_NLS */,
+                                    gg_status* statuses /* may be NULL */, void* stream);
 
 /* Multi-line accesses (replaces the line loop of Core::initiateMemoryAccess,
  * common/tile/core/core.cc:139-266, for the coherent mode).  Input: a

@@ -15,6 +15,15 @@ zeroes the NoC counters and re-initialises every router queue, ATAC's included
 state and the reported statistics are those of one batch.  The times are the
 medians over --reps passes.  Results are not verified here
 (tests/test_gpu_netgen.py does that).
+
+--many: all points of one (tile count, model) run in one
+gg_noc_synthetic_run_many call per pass, each point on a context of its own.
+The per-point lines carry the same statistics and means (the same points give
+the same figures with and without --many) and no step times; one more line per
+(tile count, model) gives the wall time of the whole sweep, "sweep_ms", the
+median over --reps passes after an untimed one.  With --compare-loop that line
+also has "loop_ms": the same contexts, reset, through gg_noc_synthetic_run one
+by one in the same process.  ATAC points keep the one-by-one path.
 """
 import argparse
 import json
@@ -43,6 +52,8 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--atac-cluster-size", type=int, default=0, help="0: 4 below 256 tiles, else 16")
+    ap.add_argument("--many", action="store_true", help="one gg_noc_synthetic_run_many call per (tiles, model) and pass")
+    ap.add_argument("--compare-loop", action="store_true", help="with --many: also time the one-by-one loop")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -57,12 +68,59 @@ def main():
         torch.cuda.synchronize()
         return r, time.perf_counter() - t0
 
+    def point_line(T, model, p, f, s, extra):
+        pk = max(int(s[B.NLS_PACKETS]), 1)
+        one = 1000.0 / f
+        d = {"tiles": T, "model": model, "pattern": B.TRAFFIC_PATTERNS[p.pattern], "offered_load": p.offered_load,
+             "packets_per_tile": args.packets, "packet_bytes": args.packet_bytes, "seed": args.seed,
+             "stats": {f_: int(s[i]) for i, f_ in enumerate(B.NLS_FIELDS)},
+             "latency_hist": {str(b): int(c) for b, c in enumerate(s[B.NLS_HIST:]) if c},
+             "mean_latency_cycles": float(s[B.NLS_LATENCY_PS]) / pk / one,
+             "mean_zero_load_cycles": float(s[B.NLS_ZERO_LOAD_PS]) / pk / one,
+             "mean_contention_cycles": float(s[B.NLS_CONTENTION_PS]) / pk / one,
+             "max_latency_cycles": float(s[B.NLS_MAX_LATENCY_PS]) / one}
+        d.update(extra)
+        print(json.dumps(d), flush=True)
+
+    def sweep_many(T, model):
+        cfg = C.default_config(T, net_model=net[model])
+        params = [B.TrafficParams(pattern, args.packet_bytes, float(load), args.packets, args.seed)
+                  for pattern in args.patterns.split(",") for load in args.loads.split(",")]
+        bes = [B.Backend(cfg) for _ in params]               # a fresh context per point
+        many, loop = [], []
+        for k in range(args.reps + 1):
+            for be in bes:
+                be.reset()
+            stats, t = clock(lambda: B.noc_synthetic_run_many(bes, params))
+            if k:
+                many.append(t)
+        for k in range((args.reps + 1) if args.compare_loop else 0):
+            for be in bes:
+                be.reset()
+            one, t = clock(lambda: [be.noc_synthetic_run(p) for be, p in zip(bes, params)])
+            if k:
+                loop.append(t)
+            if not all(np.array_equal(a, b) for a, b in zip(one, stats)):
+                sys.exit("noc_load_sweep: the loop and the --many call disagree")
+        for be in bes:
+            be.close()
+        for p, s in zip(params, stats):
+            point_line(T, model, p, cfg.frequency_ghz, s, {"reps": args.reps, "many": True})
+        line = {"tiles": T, "model": model, "points": len(params), "packets_per_tile": args.packets,
+                "sweep_ms": float(np.median(many)) * 1e3, "sweep_ms_all": [x * 1e3 for x in many], "reps": args.reps}
+        if loop:
+            line.update({"loop_ms": float(np.median(loop)) * 1e3, "loop_ms_all": [x * 1e3 for x in loop]})
+        print(json.dumps(line), flush=True)
+
     for T in [int(x) for x in args.tiles.split(",")]:
         n = T * args.packets
         ins = [torch.zeros(n, dtype=torch.int32, device=dev) for _ in range(3)] + \
               [torch.zeros(n, dtype=torch.int64, device=dev)]
         outs = [torch.zeros(n, dtype=torch.int64, device=dev) for _ in range(3)]
         for model in args.models.split(","):
+            if args.many and model != "atac":
+                sweep_many(T, model)
+                continue
             for pattern in args.patterns.split(","):
                 for load in [float(x) for x in args.loads.split(",")]:
                     cfg = C.default_config(T, net_model=net[model])
@@ -80,19 +138,9 @@ def main():
                             passes.append((tg, tr, ts))
                     be.close()
                     med = [float(np.median([x[i] for x in passes])) for i in range(3)]
-                    pk = max(int(s[B.NLS_PACKETS]), 1)
-                    one = 1000.0 / cfg.frequency_ghz
-                    print(json.dumps({
-                        "tiles": T, "model": model, "pattern": pattern, "offered_load": load,
-                        "packets_per_tile": args.packets, "packet_bytes": args.packet_bytes, "seed": args.seed,
-                        "stats": {f: int(s[i]) for i, f in enumerate(B.NLS_FIELDS)},
-                        "latency_hist": {str(b): int(c) for b, c in enumerate(s[B.NLS_HIST:]) if c},
-                        "mean_latency_cycles": float(s[B.NLS_LATENCY_PS]) / pk / one,
-                        "mean_zero_load_cycles": float(s[B.NLS_ZERO_LOAD_PS]) / pk / one,
-                        "mean_contention_cycles": float(s[B.NLS_CONTENTION_PS]) / pk / one,
-                        "max_latency_cycles": float(s[B.NLS_MAX_LATENCY_PS]) / one,
-                        "generate_ms": med[0] * 1e3, "route_ms": med[1] * 1e3, "reduce_ms": med[2] * 1e3,
-                        "reps": args.reps}), flush=True)
+                    point_line(T, model, p, cfg.frequency_ghz, s,
+                               {"generate_ms": med[0] * 1e3, "route_ms": med[1] * 1e3, "reduce_ms": med[2] * 1e3,
+                                "reps": args.reps})
 
 
 if __name__ == "__main__":
