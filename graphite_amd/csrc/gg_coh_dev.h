@@ -256,9 +256,9 @@ struct CS {
   // {first workgroup start, last workgroup end} on the s_memrealtime clock
   GG_DP unsigned long long* kt; uint32_t kt_slot, kt_stride;   // timing mode 2: per block {start, end} of launch slot kt_slot
 };
-// profile slots: step phases 0..5 summed over tiles, 8 = sum over steps of the slowest tile;
-// walker: 16 staging+load, 17 event loop, 18 hand-off+write back, 19 events, 20 sum of slowest walker per launch (X),
-// 21 (Y), 22 launches
+// S.prof's words by name: PF_*.  (In a file of its own: fail() compiles the
+// line it was called from into the kernels, so this file keeps its line count.)
+#include "gg_coh_prof.h"
 constexpr uint32_t kTrStep = 32;       // GG_COH_TRACE words per (launch, tile)
 constexpr uint32_t kTrEv0 = 200, kTrEvMax = 128;
 #define PROF_T0() const uint64_t _p0 = (DG(S.prof) || DG(S.trs)) ? __builtin_amdgcn_s_memtime() : 0
@@ -269,8 +269,8 @@ constexpr uint32_t kTrEv0 = 200, kTrEvMax = 128;
 __device__ __forceinline__ void prof_batch(const CS& S, int kind, uint32_t m, uint32_t tail)
 {
   const int b = m <= 1 ? 0 : m <= 3 ? 1 : m <= 7 ? 2 : m <= 15 ? 3 : m <= 31 ? 4 : m <= 63 ? 5 : 6;
-  atomicAdd(&DG(S.prof)[50 + 8 * kind + b], (unsigned long long)m);
-  atomicAdd(&DG(S.prof)[80 + kind], (unsigned long long)tail);
+  atomicAdd(&DG(S.prof)[PF_BATCH + PF_BATCH_KIND * kind + b], (unsigned long long)m);
+  atomicAdd(&DG(S.prof)[PF_BATCH_TAIL + kind], (unsigned long long)tail);
 }
 
 __device__ __forceinline__ gg_cmsg* pool(const CS& S, uint32_t p) { return p ? S.pool1 : S.pool0; }
@@ -1492,7 +1492,7 @@ struct Tile {
     const bool ok = mine && hit && l2ok && (e - P.lat_l1d < barrier || (wm & GG_META_CONT));
     const uint64_t m = __ballot(ok) >> o;
     const uint32_t n = ~m ? (uint32_t)__builtin_ctzll(~m) : 64u - o;
-    if (DG(S.prof) && ln == 0) { atomicAdd(&DG(S.prof)[37], (unsigned long long)__builtin_amdgcn_s_memtime()); atomicAdd(&DG(S.prof)[38], 1ull); }
+    if (DG(S.prof) && ln == 0) { atomicAdd(&DG(S.prof)[PF_HR_T_LOOKUP], (unsigned long long)__builtin_amdgcn_s_memtime()); atomicAdd(&DG(S.prof)[PF_HR_CALLS], 1ull); }
     if (!n) return 0;
     const uint64_t run = (n == 64 ? ~0ull : ((1ull << n) - 1)) << o;
     const bool inrun = (run >> ln) & 1;
@@ -1524,12 +1524,12 @@ struct Tile {
         }
       }
       PROF_AT(_q1);
-      if (DG(S.prof) && ln == 0) atomicAdd(&DG(S.prof)[40], (unsigned long long)_q1);
+      if (DG(S.prof) && ln == 0) atomicAdd(&DG(S.prof)[PF_HR_T_LOOP], (unsigned long long)_q1);
       if (lru1 && inrun) lru_run_store(L1.meta + (size_t)s1 * L1.ways, L1.ways, r1a, r1b, w1, tm1, af1);
       if (lru2 && w2l) lru_run_store(L2.meta + (size_t)s2 * L2.ways, L2.ways, r2a, r2b, w2, tm2, af2);
       L1.cset = ~0u; L2.cset = ~0u;                                  // the one-row caches reload
       PROF_AT(_q2);
-      if (DG(S.prof) && ln == 0) { atomicAdd(&DG(S.prof)[41], (unsigned long long)_q2); atomicAdd(&DG(S.prof)[42], 1ull); }
+      if (DG(S.prof) && ln == 0) { atomicAdd(&DG(S.prof)[PF_HR_T_STORE], (unsigned long long)_q2); atomicAdd(&DG(S.prof)[PF_HR_ROWS], 1ull); }
     } else if (lru1 || lru2) {                                       // > 16 ways: one touch at a time
       for (uint32_t k = 0; k < n; ++k) {
         const uint32_t l = o + k;
@@ -3212,12 +3212,12 @@ __device__ __forceinline__ uint64_t tile_step(const CP& P, const CS& S, uint32_t
 
   PROF_AT(_p1);
   if (DG(S.prof) && ln == 0 && na) {
-    atomicAdd(&DG(S.prof)[90], (unsigned long long)(_sa - _p0)); atomicAdd(&DG(S.prof)[91], (unsigned long long)(_sb - _sa));
-    atomicAdd(&DG(S.prof)[92], (unsigned long long)(_sc - _sb)); atomicAdd(&DG(S.prof)[93], (unsigned long long)(_sd - _sc));
-    atomicAdd(&DG(S.prof)[94], (unsigned long long)(_se - _sd)); atomicAdd(&DG(S.prof)[95], (unsigned long long)(_p1 - _se));
-    atomicAdd(&DG(S.prof)[96], 1ull);
+    atomicAdd(&DG(S.prof)[PF_SELF_PHASE + 0], (unsigned long long)(_sa - _p0)); atomicAdd(&DG(S.prof)[PF_SELF_PHASE + 1], (unsigned long long)(_sb - _sa));
+    atomicAdd(&DG(S.prof)[PF_SELF_PHASE + 2], (unsigned long long)(_sc - _sb)); atomicAdd(&DG(S.prof)[PF_SELF_PHASE + 3], (unsigned long long)(_sd - _sc));
+    atomicAdd(&DG(S.prof)[PF_SELF_PHASE + 4], (unsigned long long)(_se - _sd)); atomicAdd(&DG(S.prof)[PF_SELF_PHASE + 5], (unsigned long long)(_p1 - _se));
+    atomicAdd(&DG(S.prof)[PF_SELF_TILES], 1ull);
   }
-  if (DG(S.prof) && ln == 0 && !na) { atomicAdd(&DG(S.prof)[97], (unsigned long long)(_sa - _p0)); atomicAdd(&DG(S.prof)[98], 1ull); }
+  if (DG(S.prof) && ln == 0 && !na) { atomicAdd(&DG(S.prof)[PF_NOSELF_PROLOGUE], (unsigned long long)(_sa - _p0)); atomicAdd(&DG(S.prof)[PF_NOSELF_TILES], 1ull); }
   // directory request FIFO in LDS when it cannot outgrow it this step
   if (rq_fit) {
     if (pre_rq) {
@@ -3277,7 +3277,7 @@ __device__ __forceinline__ uint64_t tile_step(const CP& P, const CS& S, uint32_t
     const uint32_t* gi_ = (const uint32_t*)(gscr + 3 * P.IC);
     PROF_AT(_p1b);
     _q1b = _p1b;
-    if (DG(S.prof) && ln == 0) atomicAdd(&DG(S.prof)[9], (unsigned long long)(_p1b - _p1));
+    if (DG(S.prof) && ln == 0) atomicAdd(&DG(S.prof)[PF_STEP_ORDER], (unsigned long long)(_p1b - _p1));
     for (uint32_t j = 0; j < n && !T.failed; ++j) {
       // the message: arrival and sender from the ordering arrays, address /
       // type / requester from the gather's registers (local index < 64: no
@@ -3352,10 +3352,10 @@ __device__ __forceinline__ uint64_t tile_step(const CP& P, const CS& S, uint32_t
       }
       if (try_run) {
         PROF_AT(_h0);
-        if (DG(S.prof) && ln == 0) atomicAdd(&DG(S.prof)[39], (unsigned long long)_h0);
+        if (DG(S.prof) && ln == 0) atomicAdd(&DG(S.prof)[PF_HR_T_START], (unsigned long long)_h0);
         const uint32_t nh = T.l1_hit_run(wbase, (uint32_t)o, wa, wm, line_mask, barrier);
         PROF_AT(_h1);
-        if (DG(S.prof) && ln == 0) { atomicAdd(&DG(S.prof)[33], (unsigned long long)(_h1 - _h0)); atomicAdd(&DG(S.prof)[34], (unsigned long long)nh); }
+        if (DG(S.prof) && ln == 0) { atomicAdd(&DG(S.prof)[PF_HR_CYCLES], (unsigned long long)(_h1 - _h0)); atomicAdd(&DG(S.prof)[PF_HR_RECORDS], (unsigned long long)nh); }
         if (nh) { if (o + nh < 64) stop = T.rec; continue; }
       }
       PROF_AT(_ha);
@@ -3368,7 +3368,7 @@ __device__ __forceinline__ uint64_t tile_step(const CP& P, const CS& S, uint32_t
       if (s >= barrier && !(meta & GG_META_CONT)) break;             // a multi-line access is one instruction
       T.app_access(rl64(wa, (uint32_t)o) & line_mask, (meta & GG_META_WRITE) != 0, s);
       PROF_AT(_h2);
-      if (DG(S.prof) && ln == 0) { atomicAdd(&DG(S.prof)[35], (unsigned long long)(_h2 - _ha)); atomicAdd(&DG(S.prof)[36], 1ull); }
+      if (DG(S.prof) && ln == 0) { atomicAdd(&DG(S.prof)[PF_ACC_CYCLES], (unsigned long long)(_h2 - _ha)); atomicAdd(&DG(S.prof)[PF_ACC_COUNT], 1ull); }
     }
     W.wbase = wbase; W.wa = wa; W.wm = wm;
   }
@@ -3553,17 +3553,17 @@ __device__ __forceinline__ uint64_t tile_step(const CP& P, const CS& S, uint32_t
   }
   if (DG(S.prof) && ln == 0) {
     const uint64_t e = __builtin_amdgcn_s_memtime();
-    atomicAdd(&DG(S.prof)[0], (unsigned long long)(_p1 - _p0)); atomicAdd(&DG(S.prof)[1], (unsigned long long)(_p2 - _p1));
-    atomicAdd(&DG(S.prof)[2], (unsigned long long)(_p3 - _p2)); atomicAdd(&DG(S.prof)[3], (unsigned long long)(_p4 - _p3));
-    atomicAdd(&DG(S.prof)[4], (unsigned long long)(e - _p4));
-    atomicMax(&DG(S.prof)[1024 + (L & 65535)], (unsigned long long)(e - _p0));
-    atomicMax(&DG(S.prof)[1024 + 3 * 65536 + (L & 65535)], (unsigned long long)(na + T.nsent));
+    atomicAdd(&DG(S.prof)[PF_STEP_SELF], (unsigned long long)(_p1 - _p0)); atomicAdd(&DG(S.prof)[PF_STEP_INBOX], (unsigned long long)(_p2 - _p1));
+    atomicAdd(&DG(S.prof)[PF_STEP_TRACE], (unsigned long long)(_p3 - _p2)); atomicAdd(&DG(S.prof)[PF_STEP_PUBLISH], (unsigned long long)(_p4 - _p3));
+    atomicAdd(&DG(S.prof)[PF_STEP_WRITEBACK], (unsigned long long)(e - _p4));
+    atomicMax(&DG(S.prof)[PF_R_STEP + (L & (PF_RING - 1))], (unsigned long long)(e - _p0));
+    atomicMax(&DG(S.prof)[PF_R_STEP_REQ + (L & (PF_RING - 1))], (unsigned long long)(na + T.nsent));
     {
       // the slowest tile's shape: (total << 24) | payload, max per launch
       const uint64_t tot = (e - _p0) << 24;
       auto c8 = [](uint64_t v) { return v > 255 ? 255ull : v; };
       auto c24 = [](uint64_t v) { v >>= 8; return v > 0xFFFFFF ? 0xFFFFFFull : v; };
-      const size_t b = 1024 + 6 * 65536 + 4 * (L & 16383);
+      const size_t b = PF_R_SHAPE + 4 * (L & (PF_SHAPES - 1));
       atomicMax(&DG(S.prof)[b + 0], (unsigned long long)(tot | (c8(ni) << 16) | (c8(na) << 8) | c8(T.nsent)));
       atomicMax(&DG(S.prof)[b + 1], (unsigned long long)(tot | c24(_p1 - _p0)));
       atomicMax(&DG(S.prof)[b + 2], (unsigned long long)(tot | c24(_p2 - _p1)));
@@ -4177,8 +4177,8 @@ __device__ __forceinline__ void walk_body(const CP& P, const CS& S, uint32_t L, 
       wave_sync();
     }
     if (RQ && DG(S.prof) && ln == 0 && d_arm) {
-      atomicAdd(&DG(S.prof)[100], (unsigned long long)d_arm); atomicAdd(&DG(S.prof)[101], (unsigned long long)d_hit);
-      atomicAdd(&DG(S.prof)[102], (unsigned long long)d_cont); atomicAdd(&DG(S.prof)[103], (unsigned long long)d_miss);
+      atomicAdd(&DG(S.prof)[PF_ARM], (unsigned long long)d_arm); atomicAdd(&DG(S.prof)[PF_ARM_HIT], (unsigned long long)d_hit);
+      atomicAdd(&DG(S.prof)[PF_ARM_CONT], (unsigned long long)d_cont); atomicAdd(&DG(S.prof)[PF_ARM_MISS], (unsigned long long)d_miss);
     }
     if (regq && visited && direct && m) {
       const uint64_t qi = (uint64_t)tile_at(pos) * 6 + port;
@@ -4287,16 +4287,16 @@ __device__ __forceinline__ void walk_body(const CP& P, const CS& S, uint32_t L, 
     nev = wave_sum(ln == 0 ? nev : 0u);
     if (ln == 0) {
       const uint64_t e = __builtin_amdgcn_s_memtime();
-      atomicAdd(&DG(S.prof)[19], (unsigned long long)nev);
+      atomicAdd(&DG(S.prof)[PF_WALK_EVENTS], (unsigned long long)nev);
       if (wv == 0) {
-        atomicAdd(&DG(S.prof)[16], (unsigned long long)(_w1 - _p0)); atomicAdd(&DG(S.prof)[17], (unsigned long long)(_w2 - _w1));
-        atomicAdd(&DG(S.prof)[18], (unsigned long long)(e - _w2));
-        atomicAdd(&DG(S.prof)[22], 1ull);
-        atomicMax(&DG(S.prof)[1024 + 65536 + 2 * (L & 65535) + stage], (unsigned long long)(e - _p0));
-        atomicMax(&DG(S.prof)[46 + stage], (unsigned long long)n);         // the most packets one run held
-        if (PIPE && !sweep && n > 64) atomicAdd(&DG(S.prof)[48], 1ull);    // pipelined with second candidates
+        atomicAdd(&DG(S.prof)[PF_WALK_STAGE], (unsigned long long)(_w1 - _p0)); atomicAdd(&DG(S.prof)[PF_WALK_LOOP], (unsigned long long)(_w2 - _w1));
+        atomicAdd(&DG(S.prof)[PF_WALK_HANDOFF], (unsigned long long)(e - _w2));
+        atomicAdd(&DG(S.prof)[PF_WALK_LAUNCHES], 1ull);
+        atomicMax(&DG(S.prof)[PF_R_WALK + 2 * (L & (PF_RING - 1)) + stage], (unsigned long long)(e - _p0));
+        atomicMax(&DG(S.prof)[PF_WALK_MAXPK + stage], (unsigned long long)n);         // the most packets one run held
+        if (PIPE && !sweep && n > 64) atomicAdd(&DG(S.prof)[PF_WALK_PAST64], 1ull);    // pipelined with second candidates
       }
-      atomicMax(&DG(S.prof)[24 + stage], (unsigned long long)nev);
+      atomicMax(&DG(S.prof)[PF_WALK_MAXEV + stage], (unsigned long long)nev);
     }
   }
 }

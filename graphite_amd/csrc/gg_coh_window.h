@@ -1,7 +1,7 @@
 // gg_coh_window.h — a coherent run fed its trace in windows:
 // the launchers of the hand-over and window-state kernels (gg_coh_window.hip).
-// The host side of gg_coherent_begin_window / _next_window / _window_state is
-// in gg_coherent.hip, beside gg_coherent_begin.
+// The host side of gg_coherent_begin_window / _next_window / _window_state
+// follows the kernels there.
 #pragma once
 #include "gg_coh_dev.h"
 

@@ -1,8 +1,8 @@
-// gg_coh_window.hip — a coherent run fed its trace in windows (DESIGN.md
-// §4j), the device side of the hand-over: one thread per owned tile rebases
-// the tile's trace position to the new window's arrays, checks that the
-// window continues where the tile stands, and works out the guard and the
-// horizon the quantum end's safe-quantum rule reads (qend_window, gg_coh_dev.h).
+// gg_coh_window.hip — a coherent run fed its trace in windows.
+// The hand-over kernel: a thread per owned tile rebases its trace position,
+// checks that the window continues where the tile stands, and works out the
+// guard and horizon of qend_window (gg_coh_dev.h).  Then the host entries.
+#include "gg_coh_host.h"
 #include "gg_coh_window.h"
 
 namespace ggc {
@@ -85,3 +85,140 @@ void launch_window_state(const CP& P, const CS& S, uint64_t* consumed, uint64_t*
 }
 
 }  // namespace ggc
+
+using namespace ggc;
+using namespace gg;
+
+// ---- the host side: gg_coherent_begin_window / _next_window / _window_state ----
+// the backstop of a windowed run (qend_window): the safe-quantum rule let a
+// tile run off a window that is not the end of its trace
+gg_status coh_window_exhausted()
+{
+  return gg_fail(GG_ERR_STATE, "coherent mode: window exhausted (a tile reached the end of a window that is not the "
+                               "end of its trace; the run's results are void)");
+}
+
+// a window's offsets and final flags onto the device; the host-side checks
+// both entries share
+static gg_status win_upload(gg_ctx* ctx, const char* what, const gg_trace* win, const uint8_t* final_tiles, hipStream_t s)
+{
+  gg_coh_state* C = ctx->coh;
+  const uint32_t T = C->P.T;
+  if (gg_status st = coh_trace_check(win, T, what)) return st;
+  if (!C->win_dev) {
+    if (gg_status st = C->mem.alloc(&C->win_dev, (uint64_t)WN_HDR + (uint64_t)C->P.L * WN_TILE)) return st;
+    if (gg_status st = C->mem.alloc(&C->win_fin_dev, (uint64_t)T)) return st;
+    if (gg_status st = C->mem.alloc(&C->win_bad_dev, 2)) return st;
+    if (gg_status st = C->mem.alloc(&C->win_state_dev, 2 * (uint64_t)T)) return st;
+  }
+  // (offs_dev is read by k_c_reset at begin only: between begins it stages a window's offsets)
+  GG_HIP(hipMemcpyAsync(C->offs_dev, win->tile_offsets, sizeof(uint64_t) * (T + 1), hipMemcpyHostToDevice, s));
+  if (final_tiles) GG_HIP(hipMemcpyAsync(C->win_fin_dev, final_tiles, T, hipMemcpyHostToDevice, s));
+  else GG_HIP(hipMemsetAsync(C->win_fin_dev, 0, T, s));
+  const uint32_t bad0[2] = {0u, ~0u};
+  GG_HIP(hipMemcpyAsync(C->win_bad_dev, bad0, sizeof(bad0), hipMemcpyHostToDevice, s));
+  GG_HIP(hipStreamSynchronize(s));                     // (the sources are the caller's and a stack array)
+  return GG_OK;
+}
+
+gg_status gg_coherent_begin_window(gg_ctx* ctx, const gg_trace* win, uint64_t* access_out_dev, const uint8_t* final_tiles,
+                                   void* stream)
+{
+  const char* const what = "gg_coherent_begin_window";
+  GG_NOT_ATAC(ctx, what);
+  if (!ctx || !win || !win->tile_offsets) return gg_fail(GG_ERR_INVALID, "%s: NULL argument", what);
+  if (gg_status st = coh_owns_all(ctx, GG_ERR_UNSUPPORTED, what)) return st;
+  hipSetDevice(ctx->device);
+  if (gg_status st = coh_alloc(ctx)) return st;
+  gg_coh_state* C = ctx->coh;
+  if (C->P.lat_l1d == 0)
+    return gg_fail(GG_ERR_UNSUPPORTED, "%s: with zero L1-D data cycles a record can cost no time, so no window "
+                                       "bounds what a tile consumes in a quantum", what);
+  for (uint32_t t = 0; t < C->P.T; ++t)
+    if (win->tile_offsets[t] == win->tile_offsets[t + 1] && !(final_tiles && final_tiles[t]))
+      return gg_fail(GG_ERR_INVALID, "%s: tile %u is not final and its window holds no record", what, t);
+  hipStream_t s = (hipStream_t)stream;
+  if (gg_status st = gg_coherent_begin(ctx, win, access_out_dev, stream)) return st;
+  // from here a failure leaves no begun run: a begun run over the first
+  // window alone would take the end of each window for the end of a trace
+  auto install = [&]() -> gg_status {
+    if (gg_status st = win_upload(ctx, what, win, final_tiles, s)) return st;
+    cs_set(C->S.win, C->win_dev);
+    const uint64_t w0[WN_HDR] = {~0ull, ~0ull};
+    GG_HIP(hipMemcpyAsync(C->win_dev, w0, sizeof(w0), hipMemcpyHostToDevice, s));
+    GG_HIP(hipMemcpyAsync(C->Sd, &C->S, sizeof(CS), hipMemcpyHostToDevice, s));
+    launch_window_install(C->P, C->S, win->addr_dev, win->meta_dev, C->offs_dev, C->win_fin_dev, 0, C->win_bad_dev, s);
+    GG_HIP(hipGetLastError());
+    GG_HIP(hipStreamSynchronize(s));
+    return GG_OK;
+  };
+  if (gg_status st = install()) { C->begun = false; C->windowed = false; C->S.win = nullptr; return st; }
+  C->windowed = true;
+  C->drv = gg_coh_state::DRV_DEVICE;                 // only gg_coherent_advance drives a windowed run
+  return GG_OK;
+}
+
+gg_status gg_coherent_next_window(gg_ctx* ctx, const gg_trace* win, uint64_t* access_out_dev, const uint8_t* final_tiles,
+                                  void* stream)
+{
+  const char* const what = "gg_coherent_next_window";
+  GG_NOT_ATAC(ctx, what);
+  if (!ctx || !win || !win->tile_offsets) return gg_fail(GG_ERR_INVALID, "%s: NULL argument", what);
+  gg_coh_state* C = ctx->coh;
+  if (!C || !C->begun || !C->windowed) return gg_fail(GG_ERR_INVALID, "%s: gg_coherent_begin_window first", what);
+  hipSetDevice(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  GG_HIP(hipStreamSynchronize(ctx->last_stream));
+  uint64_t done = 0;
+  uint32_t err = 0;
+  GG_HIP(hipMemcpy(&done, C->S.qs + QS_DONE, sizeof(done), hipMemcpyDeviceToHost));
+  GG_HIP(hipMemcpy(&err, ctx->err_dev, sizeof(err), hipMemcpyDeviceToHost));
+  if ((done & 3) || err)
+    return gg_fail(GG_ERR_INVALID, "%s: the run is not at the device loop's clean point (it is over or has failed); "
+                                   "a window goes in after begin or a paused gg_coherent_advance", what);
+  if (gg_status st = win_upload(ctx, what, win, final_tiles, s)) return st;
+  launch_window_install(C->P, C->S, win->addr_dev, win->meta_dev, C->offs_dev, C->win_fin_dev, 1, C->win_bad_dev, s);
+  GG_HIP(hipGetLastError());
+  uint32_t bad[2] = {0, 0};
+  GG_HIP(hipMemcpyAsync(bad, C->win_bad_dev, sizeof(bad), hipMemcpyDeviceToHost, s));
+  GG_HIP(hipStreamSynchronize(s));
+  if (bad[0]) {
+    const uint32_t t = bad[1] - 1;
+    const char* why = (bad[0] & WB_STATE)  ? "a tile stands past the end of its window"
+                    : (bad[0] & WB_EMPTY)  ? "an unfinished tile's window holds no record"
+                    : (bad[0] & WB_RECORD) ? "a window's first record is not the record its tile stands on (addr or meta)"
+                    : (bad[0] & WB_FINAL)  ? "a final tile made non-final, or with another number of records left"
+                                           : "a finished tile's range is not empty";
+    return gg_fail(GG_ERR_INVALID, "%s: %s (first at tile %u); nothing changed", what, why, t);
+  }
+  const uint64_t hor0 = ~0ull;
+  GG_HIP(hipMemcpyAsync(C->win_dev + WN_HOR, &hor0, sizeof(hor0), hipMemcpyHostToDevice, s));
+  launch_window_install(C->P, C->S, win->addr_dev, win->meta_dev, C->offs_dev, C->win_fin_dev, 2, C->win_bad_dev, s);
+  GG_HIP(hipGetLastError());
+  cs_set(C->S.addr, win->addr_dev); cs_set(C->S.meta, win->meta_dev); cs_set(C->S.out, access_out_dev);
+  GG_HIP(hipMemcpyAsync(C->Sd, &C->S, sizeof(CS), hipMemcpyHostToDevice, s));
+  GG_HIP(hipStreamSynchronize(s));                     // the old arrays are the caller's again
+  C->n_records = win->num_records;
+  C->offs_host.assign(win->tile_offsets, win->tile_offsets + C->P.T + 1);
+  ctx->last_stream = s;
+  return GG_OK;
+}
+
+gg_status gg_coherent_window_state(gg_ctx* ctx, uint64_t* consumed, uint64_t* min_records)
+{
+  const char* const what = "gg_coherent_window_state";
+  GG_NOT_ATAC(ctx, what);
+  if (!ctx) return gg_fail(GG_ERR_INVALID, "%s: NULL argument", what);
+  gg_coh_state* C = ctx->coh;
+  if (!C || !C->begun || !C->windowed) return gg_fail(GG_ERR_INVALID, "%s: gg_coherent_begin_window first", what);
+  hipSetDevice(ctx->device);
+  hipStream_t s = ctx->last_stream;
+  const uint32_t T = C->P.T;
+  GG_HIP(hipMemsetAsync(C->win_state_dev, 0, sizeof(uint64_t) * 2 * T, s));
+  launch_window_state(C->P, C->S, C->win_state_dev, C->win_state_dev + T, s);
+  GG_HIP(hipGetLastError());
+  GG_HIP(hipStreamSynchronize(s));
+  if (consumed) GG_HIP(hipMemcpy(consumed, C->win_state_dev, sizeof(uint64_t) * T, hipMemcpyDeviceToHost));
+  if (min_records) GG_HIP(hipMemcpy(min_records, C->win_state_dev + T, sizeof(uint64_t) * T, hipMemcpyDeviceToHost));
+  return GG_OK;
+}

@@ -11,7 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "..", "graphite_amd", "csrc")
 UNITS = ["gg_cache", "gg_core", "gg_coh_step", "gg_coh_step_fast", "gg_coh_step_mosi", "gg_coh_step_shl2",
-         "gg_coh_persist", "gg_coh_persist_lc", "gg_coh_walk"]
+         "gg_coh_persist", "gg_coh_persist_lc", "gg_coh_walk", "gg_coh_many"]
 FIELDS = ["TotalSGPRs", "VGPRs", "SGPRs Spill", "VGPRs Spill", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]",
           "Occupancy [waves/SIMD]"]
 
