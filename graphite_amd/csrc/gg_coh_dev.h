@@ -3989,7 +3989,12 @@ __device__ __forceinline__ void walk_body(const CP& P, const CS& S, uint32_t L, 
     const uint32_t status_nx =                                         // next router in another shard: held
         (uint32_t)__builtin_amdgcn_readfirstlane((int)((nx < sd.lo || nx > sd.hi) ? 2u : 0u));
     const uint64_t zk = zps << 12;                                     // a port's router + link delay, in keys
-    uint64_t cq = 0, cf = 0, m = 0;
+    // what this launch's serves add to the port's counters and, with register
+    // queues, to the queue's M/G/1 sums (RegQueue::Delta: the sums themselves
+    // stay what finish() loaded until store()): dq.n is the served count,
+    // dq.p the flits
+    uint64_t cq = 0;
+    RegQueue::Delta dq{};
     uint32_t spin = 0, polls = 0;
     const bool tev = DG(S.tre) && L >= kTrEv0 && L < kTrEv0 + S.tre_n;
     unsigned long long* tre = tev ? DG(S.tre) + (((size_t)(L - kTrEv0) * 2 + stage) * S.tr_wb + blk) * (kTrEvMax * 4 + 4) : nullptr;
@@ -4117,9 +4122,16 @@ __device__ __forceinline__ void walk_body(const CP& P, const CS& S, uint32_t L, 
           const uint32_t status = status_nx ? status_nx : (nx == (cfd >> 24) ? 1u : 0u);
           rq.prune();
           const uint64_t tc_ = rfl64(time_to_cycles(Tc, P.np.f));
-          fs = rq.search(tc_, nf_);
+          fs = rq.search(tc_, nf_, dq);
           fs.qd = rfl64(fs.qd);
-          const uint64_t fwd = pipe_word(Tc + zps + rfl64(lat_to_ps(fs.qd, P.np.f)), nx, status);
+          // (held in a vector register pair from here on: left to itself the
+          // compiler forms the word after the hit, from spilled scalars.  This
+          // rests on what the register allocator does today: after a compiler
+          // update compare the armed hit, from the s_cmp_eq_u64 of the poll to
+          // the ds_write_b64, with the listing in profiles/r19/README.md —
+          // no v_readlane_b32 between them)
+          uint64_t fwd = pipe_word(Tc + zps + rfl64(lat_to_ps(fs.qd, P.np.f)), nx, status);
+          asm volatile("" : "+v"(fwd));
           uint64_t seen = GG_COH_DIAG ? rl64(ci < 64 ? w0 : w1, bl) : 0;
           if (GG_COH_DIAG) ++d_arm;
           // ---- armed poll: one LDS load
@@ -4165,13 +4177,14 @@ __device__ __forceinline__ void walk_body(const CP& P, const CS& S, uint32_t L, 
         if (!qm) pub(0ull);
         else {
           tc = rfl64(time_to_cycles(T, P.np.f));
-          if (regq) { rq.prune(); fs = rq.search(tc, nf); qd = fs.qd; pub(qd); }
+          if (regq) { rq.prune(); fs = rq.search(tc, nf, dq); qd = fs.qd; pub(qd); }
           else { qd = wave_q ? tr.delay_w(tc, nf, S.err, ln) : tr.delay(tc, nf, S.err); pub(qd); }
         }
       }
-      if (regq) rq.apply(tc, nf, fs);
+      if (regq) rq.apply(tc, nf, fs, dq);
+      else { ++dq.n; dq.p += nf; }                   // no register queue: the port's two counters only
       const uint64_t ev1 = tev ? __builtin_amdgcn_s_memtime() : 0;
-      cq += qd; cf += nf; ++m;
+      cq += qd;
       if (ln == (i & 63)) { if (i < 64) c0 = false; else c1 = false; }   // served here: no longer a candidate
       if (tev) rec_ev(ev0, evp, ev1, i, polls);
       wave_sync();
@@ -4180,14 +4193,14 @@ __device__ __forceinline__ void walk_body(const CP& P, const CS& S, uint32_t L, 
       atomicAdd(&DG(S.prof)[PF_ARM], (unsigned long long)d_arm); atomicAdd(&DG(S.prof)[PF_ARM_HIT], (unsigned long long)d_hit);
       atomicAdd(&DG(S.prof)[PF_ARM_CONT], (unsigned long long)d_cont); atomicAdd(&DG(S.prof)[PF_ARM_MISS], (unsigned long long)d_miss);
     }
-    if (regq && visited && direct && m) {
+    if (regq && visited && direct && dq.n) {
       const uint64_t qi = (uint64_t)tile_at(pos) * 6 + port;
-      rq.errp = S.err; rq.store(S.nq + qi, S.nnd + qi * P.np.max_size);
+      rq.errp = S.err; rq.store(S.nq + qi, S.nnd + qi * P.np.max_size, dq);
     } else if (regq && visited && !direct) {
-      rq.errp = S.err; rq.store(tr.q, tr.nd);
+      rq.errp = S.err; rq.store(tr.q, tr.nd, dq);
     }
-    if (ln == 0 && visited) add_ctr(pos, cq, m, cf);
-    nev = (uint32_t)m;
+    if (ln == 0 && visited) add_ctr(pos, cq, dq.n, dq.p);
+    nev = (uint32_t)dq.n;
   }
   if (tid < n) {
     const uint32_t hx = tile_at(pos_of(pdst));

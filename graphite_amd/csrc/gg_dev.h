@@ -569,15 +569,40 @@ struct RegQueue {
     a0 = v0 ? r.x0.first : 0; b0 = v0 ? r.x0.second : 0;
     a1 = v1 ? r.x1.first : 0; b1 = v1 ? r.x1.second : 0;
   }
-  __device__ __forceinline__ void store(HQueue* q, HNode* nd) const
+  // Deferred accounting (the pipelined walker): the eight sums stay what
+  // load() / finish() read — base values, invariant in the loop around the
+  // requests — and the loop carries what its requests add to them: five
+  // wave-uniform values for eight (sig and util take the same sum of p, n and
+  // total_req the same count, newest and last_req the same maximum), updated
+  // with scalar adds and one scalar maximum.  store() writes base + delta;
+  // integer adds and maxima are associative, so the header is what account()
+  // after every request leaves.  por (every p or-ed) is for the range flag.
+  struct Delta {                       // (an aggregate: Delta{} is all zero)
+    uint64_t n, p, p2, mx, anl, por;
+    __device__ __forceinline__ void add(uint64_t t, uint64_t pp, uint64_t qd)
+    {
+      ++n; p += pp; p2 += pp * pp; por |= pp;
+      const uint64_t x = t + qd + pp;
+      mx = x > mx ? x : mx;
+    }
+  };
+  __device__ __forceinline__ void store(HQueue* q, HNode* nd) const { store(q, nd, Delta{}); }
+  __device__ __forceinline__ void store(HQueue* q, HNode* nd, const Delta& d) const
   {
-    if (errs && errp && ln == 0) atomicOr(errp, errs);
+    uint32_t e = errs;
+    const uint64_t ss = sig_sq + d.p2;
+    // account()'s range check once for the batch: sig_sq only grows, so the
+    // last value tells whether any was out of range, and some p had a bit at
+    // or above 2^26 iff their or has
+    if (d.n && (ss >= kMg1Exact || (d.por >> 26))) e |= GG_DERR_RANGE;
+    if (e && errp && ln == 0) atomicOr(errp, e);
     const uint32_t l0 = li(), l1 = l0 ^ 64u;
     if (l0 < sz) nd[l0] = HNode{a0, b0};
     if (l1 < sz) nd[l1] = HNode{a1, b1};
     q->size = sz; q->head = 0;
-    q->sig_sq = sig_sq; q->sig = sig; q->n = nreq; q->newest = newest;
-    q->util = util; q->last_req = last_req; q->total_req = total_req; q->analytical = anl;
+    q->sig_sq = ss; q->sig = sig + d.p; q->n = nreq + d.n; q->newest = d.mx > newest ? d.mx : newest;
+    q->util = util + d.p; q->last_req = d.mx > last_req ? d.mx : last_req; q->total_req = total_req + d.n;
+    q->analytical = anl + d.anl;
   }
   // this lane's logical index in slot 0 (slot 1: the same ^ 64), and the
   // position of logical interval i
@@ -633,7 +658,9 @@ struct RegQueue {
   // pipelined walker's loop joins branches on values loaded from memory and
   // holds the sums in VGPRs whatever is done here, so a read-back there is 16
   // readfirstlane and as many copies back a serve (-2.9 % of k_c_walk
-  // without it; profiles/r15).
+  // without it; profiles/r15) — that loop now carries a Delta instead and
+  // never comes here.  The NoC batches choose at their call sites
+  // (request<TAIL, RB>; profiles/r19).
   template <bool RB> __device__ __forceinline__ static uint64_t rd64(uint64_t v) { return RB ? rfl64(v) : v; }
   template <bool RB> __device__ __forceinline__ void account(uint64_t t, uint64_t p, uint64_t qd)
   {
@@ -680,7 +707,9 @@ struct RegQueue {
     hd = full ? (hd + 1) & 127u : hd;
     sz = full ? sz - 1 : sz;
   }
-  __device__ __forceinline__ Found search(uint64_t t, uint64_t p) const
+  // d: what the batch has added to the sums so far under deferred accounting
+  // (the analytical branch forms base + delta here; nothing else reads them)
+  __device__ __forceinline__ Found search(uint64_t t, uint64_t p, const Delta& d = Delta{}) const
   {
     const uint64_t tp = t + p;
     const uint32_t hd = rd32(this->hd), sz = rd32(this->sz);
@@ -695,7 +724,9 @@ struct RegQueue {
     const uint32_t hs = hd & 63u;
     if (analytical) {                                                // interval 0 (position hd) starts after t + p
       const uint64_t g = hd < 64 ? cmp64<kCmpUGT>(a0, tp) : cmp64<kCmpUGT>(a1, tp);
-      if ((g >> hs) & 1ull) return Found{rfl64(mg1_queue_delay(nreq, newest, sig_sq, sig)), 0u, kAnalytical};
+      if ((g >> hs) & 1ull)
+        return Found{rfl64(mg1_queue_delay(nreq + d.n, d.mx > newest ? d.mx : newest, sig_sq + d.p2, sig + d.p)), 0u,
+                     kAnalytical};
     }
     const uint64_t m0 = ~le0 & v0 & cmp64<kCmpUGE>(b0 - a0, p);      // the first later interval long enough
     const uint64_t m1 = ~le1 & v1 & cmp64<kCmpUGE>(b1 - a1, p);
@@ -713,8 +744,21 @@ struct RegQueue {
   // bound of ui, and of two parts the left one is ui with end t, the right
   // one ui + 1 with start t+p: two selects on the lanes' logical index, one
   // writing starts and one ends.  A fit that keeps neither part erases the
-  // interval behind that.  RB: see account().
+  // interval behind that.  update() is the interval list's half of apply()
+  // (true: the request was analytical, which changes no interval); the sums
+  // follow at once (apply(t, p, s); RB: see account()) or as deltas
+  // (apply(t, p, s, d)).
   template <bool RB = false> __device__ __forceinline__ void apply(uint64_t t, uint64_t p, const Found& s)
+  {
+    if (update(t, p, s)) ++anl;
+    account<RB>(t, p, s.qd);
+  }
+  __device__ __forceinline__ void apply(uint64_t t, uint64_t p, const Found& s, Delta& d)
+  {
+    d.anl += update(t, p, s) ? 1u : 0u;
+    d.add(t, p, s.qd);
+  }
+  __device__ __forceinline__ bool update(uint64_t t, uint64_t p, const Found& s)
   {
     const uint64_t tp = t + p;
     const uint32_t ui = rd32(s.ui), kind = rd32(s.kind);
@@ -733,7 +777,7 @@ struct RegQueue {
       sz += split ? 1u : 0u;
       if (!keepL && !keepR) { shift_down(ui); --sz; }
     } else if (kind == kAnalytical) {
-      ++anl; ++n_anl;
+      ++n_anl;
     } else if (kind == kNone) {
       ++n_gen;
       errs |= GG_DERR_STATE;
@@ -743,7 +787,7 @@ struct RegQueue {
       if (b - (a + p) >= min_proc) set(ui, a + p, b);
       else { shift_down(ui); --sz; }
     }
-    account<RB>(t, p, s.qd);
+    return kind == kAnalytical;
   }
   // computeQueueDelay (queue_model_history_tree.cc:44-126) + QueueModelMG1::updateQueue.
   // The O(1) branch for a request served by the last interval stands in
@@ -751,8 +795,9 @@ struct RegQueue {
   // branch for requests served by the last two intervals (in-order streams:
   // SELF / injection ports); the walkers' requests land mid-list 84 % of the
   // time and skip that check (TAIL = false: search + apply serve those
-  // requests too, with the same result).
-  template <bool TAIL = true>
+  // requests too, with the same result).  RB: see account(); the caller
+  // chooses by what its loop around the requests carries the sums in.
+  template <bool TAIL = true, bool RB = true>
   __device__ __forceinline__ uint64_t request(uint64_t t, uint64_t p, uint32_t* err)
   {
     errp = err;
@@ -763,7 +808,7 @@ struct RegQueue {
         ++n_fast;
         if (t - la >= min_proc) { set(sz - 1, la, t); set(sz, t + p, lb); ++sz; }
         else set(sz - 1, t + p, lb);
-        account<true>(t, p, 0);
+        account<RB>(t, p, 0);
         return 0;
       }
       if (TAIL && sz >= 2 && t < la && t >= A(sz - 2)) {
@@ -788,12 +833,12 @@ struct RegQueue {
           if (lb - (la + p) >= min_proc) set(i1, la + p, lb);
           else --sz;                                                   // erase the last interval
         }
-        account<true>(t, p, qd);
+        account<RB>(t, p, qd);
         return qd;
       }
     }
     const Found s = search(t, p);
-    apply<true>(t, p, s);
+    apply<RB>(t, p, s);
     return s.qd;
   }
 };

@@ -453,6 +453,9 @@ __device__ void chain_staged(NocDev D, int stage, const uint32_t* __restrict__ d
 constexpr uint32_t kSweepPk = 6144, kSweepSort = 8192, kSweepPos = 256, kSweepThreads = 256;
 static_assert(sizeof(Ev) >= 2 * sizeof(SK), "start runs + arrivals fit a bucket's Ev scratch");
 constexpr size_t kSweepLds = (size_t)kSweepSort * sizeof(SK) + (size_t)kSweepPk * 4 + kSweepPos * 8 + 64;
+// RegQueue::request's read-back of the M/G/1 sums at the batch kernels' call
+// sites (request<TAIL, RB>; measured both ways in profiles/r19)
+constexpr bool kNocRB = false;
 
 __device__ void chain_sweep(NocDev D, int stage, const uint32_t* __restrict__ dst,
     const uint32_t* __restrict__ len, const uint64_t* __restrict__ bucket_off, uint32_t* __restrict__ bucket_ids,
@@ -544,7 +547,7 @@ __device__ void chain_sweep(NocDev D, int stage, const uint32_t* __restrict__ ds
         for (uint32_t j = 0; j < cnt; ++j) {
           const uint64_t t = rl64(myt, j);
           const uint32_t nf = (uint32_t)__builtin_amdgcn_readlane((int)myinfo, (int)j) & 0xFFFFu;
-          const uint64_t qd = P.qm ? rq.request<true>(time_to_cycles(t, P.f), nf, D.err) : 0;
+          const uint64_t qd = P.qm ? rq.request<true, kNocRB>(time_to_cycles(t, P.f), nf, D.err) : 0;
           cq += qd; cf += nf;
           if (ln == j) out = t + zps + lat_to_ps(qd, P.f);
         }
@@ -849,8 +852,8 @@ __device__ __forceinline__ void chain_pipe(const NocDev& D, int stage, const uin
             const uint64_t t = rl64(x.t, jj);
             const uint32_t nf = (uint32_t)__builtin_amdgcn_readlane((int)inf, (int)jj) & 0xFFFFu;
             uint64_t qd = 0;
-            if (P.qm) qd = j == 0 ? pp[0].rq.request<true>(time_to_cycles(t, P.f), nf, D.err)
-                                  : pp[kPipeK - 1].rq.request<true>(time_to_cycles(t, P.f), nf, D.err);
+            if (P.qm) qd = j == 0 ? pp[0].rq.request<true, kNocRB>(time_to_cycles(t, P.f), nf, D.err)
+                                  : pp[kPipeK - 1].rq.request<true, kNocRB>(time_to_cycles(t, P.f), nf, D.err);
             if (j == 0) { pp[0].cq += qd; pp[0].cf += nf; } else { pp[kPipeK - 1].cq += qd; pp[kPipeK - 1].cf += nf; }
             if (ln == jj) out = t + zps + lat_to_ps(qd, P.f);
           }
@@ -981,7 +984,7 @@ __device__ __forceinline__ void port_sweep(const NocDev& D, const uint32_t* __re
     for (uint32_t j = 0; j < cnt; ++j) {
       const uint64_t t = rl64(myt, j);
       const uint32_t nf = (uint32_t)__builtin_amdgcn_readlane((int)mynf, (int)j);
-      const uint64_t qd = P.qm ? rq.request<true>(time_to_cycles(t, P.f), nf, D.err) : 0;
+      const uint64_t qd = P.qm ? rq.request<true, kNocRB>(time_to_cycles(t, P.f), nf, D.err) : 0;
       cq += qd;
       if (ln == j) qmine = qd;
     }
