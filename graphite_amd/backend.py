@@ -11,7 +11,7 @@ import os
 import numpy as np
 
 from .config import (GGConfig, NUM_CACHE_COUNTERS, NUM_NET_COUNTERS, NUM_TILE_STATS, NUM_RUN_INFO, NUM_CORE_STATS,
-                     CMSG_DTYPE, AtacParams, NUM_ATAC_COUNTERS)
+                     CMSG_DTYPE, AtacParams, NUM_ATAC_COUNTERS, MemTrafficParams, NUM_MEM_INS_TYPES, NUM_MLS)
 
 CMSG_BYTES = CMSG_DTYPE.itemsize
 
@@ -69,7 +69,9 @@ EXPORTS = ["gg_abi_version", "gg_last_error", "gg_config_default", "gg_create", 
            "gg_coherent_advance_many",
            "gg_coherent_begin_window", "gg_coherent_next_window", "gg_coherent_window_state",
            "gg_traffic_params_default", "gg_gen_network_traffic", "gg_noc_latency_stats", "gg_noc_synthetic_run",
-           "gg_noc_route_batch_many", "gg_noc_synthetic_run_many"]
+           "gg_noc_route_batch_many", "gg_noc_synthetic_run_many",
+           "gg_mem_traffic_params_default", "gg_gen_memory_traffic", "gg_mem_latency_stats", "gg_mem_synthetic_run",
+           "gg_mem_synthetic_get", "gg_mem_synthetic_copy"]
 
 # synthetic network traffic (gg_gen_network_traffic): GG_TP_* patterns, GG_NLS_* words of the reduction
 TRAFFIC_PATTERNS = ["uniform_random", "bit_complement", "shuffle", "transpose", "tornado", "nearest_neighbor"]
@@ -222,6 +224,18 @@ def load():
                                             ctypes.POINTER(i32), vp]
     for name in ["gg_gen_network_traffic", "gg_noc_latency_stats", "gg_noc_synthetic_run", "gg_noc_route_batch_many",
                  "gg_noc_synthetic_run_many"]:
+        getattr(L, name).restype = i32
+    L.gg_mem_traffic_params_default.argtypes = [ctypes.POINTER(MemTrafficParams)]
+    L.gg_mem_traffic_params_default.restype = None
+    L.gg_gen_memory_traffic.argtypes = [ctypes.POINTER(MemTrafficParams), u32, u32, vp, ctypes.POINTER(u64), vp, vp, u64,
+                                        vp, vp, vp]
+    L.gg_mem_latency_stats.argtypes = [ctypes.POINTER(_Trace), vp, vp, vp]
+    L.gg_mem_synthetic_run.argtypes = [vp, ctypes.POINTER(MemTrafficParams), vp, vp]
+    L.gg_mem_synthetic_get.argtypes = [vp, ctypes.POINTER(_Trace), ctypes.POINTER(vp), ctypes.POINTER(vp),
+                                       ctypes.POINTER(vp)]
+    L.gg_mem_synthetic_copy.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    for name in ["gg_gen_memory_traffic", "gg_mem_latency_stats", "gg_mem_synthetic_run", "gg_mem_synthetic_get",
+                 "gg_mem_synthetic_copy"]:
         getattr(L, name).restype = i32
     for name in ["gg_kernel_stats", "gg_shard_map", "gg_coherent_begin", "gg_coherent_quantum", "gg_coherent_export",
                  "gg_coherent_import", "gg_coherent_run", "gg_coherent_get_stats", "gg_gen_hotspot_trace",
@@ -402,6 +416,35 @@ class Backend:
         _check(load().gg_noc_synthetic_run(self.h, ctypes.byref(params), stats.ctypes.data_as(ctypes.c_void_p),
                                            _stream(stream)))
         return stats
+
+    def mem_synthetic_run(self, params, stream=None):
+        """gg_mem_synthetic_run: generate params' (config.MemTrafficParams)
+        instruction stream for this context's tiles and line size, run it with
+        gg_coherent_run and reduce its access words; returns the NUM_MLS words
+        (config.MLS_*), the type totals and the max tile clock among them."""
+        stats = np.zeros(NUM_MLS, np.uint64)
+        _check(load().gg_mem_synthetic_run(self.h, ctypes.byref(params), stats.ctypes.data_as(ctypes.c_void_p),
+                                           _stream(stream)))
+        return stats
+
+    def mem_synthetic_trace(self, stream=None):
+        """The last mem_synthetic_run's trace and results in fresh device
+        tensors (gg_mem_synthetic_get for the sizes and tile offsets,
+        gg_mem_synthetic_copy for the arrays): (addr, meta, tile_offsets
+        [host], access words, tails [tiles], type counts [tiles][6]) — addr,
+        meta and tile_offsets go to any coherent driver as they are."""
+        import torch
+        tr = _Trace()
+        _check(load().gg_mem_synthetic_get(self.h, ctypes.byref(tr), None, None, None))
+        T, n = self.cfg.num_tiles, int(tr.num_records)
+        offs = np.array([tr.tile_offsets[i] for i in range(T + 1)], np.uint64)
+        addr, out = (torch.zeros(n, dtype=torch.int64, device="cuda") for _ in range(2))
+        meta = torch.zeros(n, dtype=torch.int32, device="cuda")
+        tail = torch.zeros(T, dtype=torch.int64, device="cuda")
+        types = torch.zeros((T, NUM_MEM_INS_TYPES), dtype=torch.int64, device="cuda")
+        _check(load().gg_mem_synthetic_copy(self.h, _ptr(addr), _ptr(meta), _ptr(out), _ptr(tail), _ptr(types),
+                                            _stream(stream)))
+        return addr, meta, offs, out, tail, types
 
     def noc_set_atac(self, params):
         """gg_noc_set_atac: the ATAC settings (config.AtacParams) of a NET_ATAC
@@ -894,6 +937,44 @@ def noc_latency_stats(src, dst, length_bits, time_ps, arrival, zero_load, conten
     stats = np.zeros(NUM_NLS, np.uint64)
     _check(load().gg_noc_latency_stats(ctypes.byref(pk), ctypes.byref(out), stats.ctypes.data_as(ctypes.c_void_p),
                                        _stream(stream)))
+    return stats
+
+
+def gen_memory_traffic(params, num_tiles, line_bytes=64, stream=None):
+    """gg_gen_memory_traffic, both steps: plan (tile offsets and the record
+    total), then fill into fresh device tensors.  Returns (addr int64, meta
+    int32, tile_offsets [host uint64, num_tiles + 1], tail_cycles int64
+    [tiles], type_counts int64 [tiles][6]); addr, meta and tile_offsets are a
+    trace for any coherent driver."""
+    import torch
+    L = load()
+    offs = np.zeros(num_tiles + 1, np.uint64)
+    total = ctypes.c_uint64(0)
+    po = offs.ctypes.data_as(ctypes.c_void_p)
+    _check(L.gg_gen_memory_traffic(ctypes.byref(params), num_tiles, line_bytes, po, ctypes.byref(total), None, None, 0,
+                                   None, None, _stream(stream)))
+    n = int(total.value)
+    addr = torch.zeros(max(n, 1), dtype=torch.int64, device="cuda")
+    meta = torch.zeros(max(n, 1), dtype=torch.int32, device="cuda")
+    tail = torch.zeros(num_tiles, dtype=torch.int64, device="cuda")
+    types = torch.zeros((num_tiles, NUM_MEM_INS_TYPES), dtype=torch.int64, device="cuda")
+    _check(L.gg_gen_memory_traffic(ctypes.byref(params), num_tiles, line_bytes, po, ctypes.byref(total), _ptr(addr),
+                                   _ptr(meta), n, _ptr(tail), _ptr(types), _stream(stream)))
+    return addr[:n], meta[:n], offs, tail, types
+
+
+def mem_latency_stats(meta, access_out, stream=None):
+    """gg_mem_latency_stats: the NUM_MLS words (config.MLS_*) of a coherent
+    run's access words, reduced on the device; meta is the trace's (BARRIER
+    records are skipped, CONT records counted)."""
+    import torch
+    n = meta.numel()
+    _need_dev(meta, torch.int32, n)
+    _need_dev(access_out, torch.int64, n)
+    tr = _Trace(None, meta.data_ptr() if n else None, None, n)
+    stats = np.zeros(NUM_MLS, np.uint64)
+    _check(load().gg_mem_latency_stats(ctypes.byref(tr), _ptr(access_out) if n else None,
+                                       stats.ctypes.data_as(ctypes.c_void_p), _stream(stream)))
     return stats
 
 

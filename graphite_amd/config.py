@@ -149,6 +149,64 @@ class AtacParams(ctypes.Structure):
             setattr(self, k, v)
 
 
+# synthetic memory traffic (gg_gen_memory_traffic): GG_MI_* instruction types, GG_MLS_* words of the reduction
+MEM_INS_TYPES = ["non_memory", "rd_only_shared_read", "rd_wr_shared_read", "rd_wr_shared_write", "private_read",
+                 "private_write"]
+NUM_MEM_INS_TYPES = 6
+MLS_FIELDS = ["records", "reads", "writes", "l1_hits", "l1_latency_ps", "l2_hits", "l2_latency_ps", "l2_misses",
+              "l2_miss_latency_ps", "max_latency_ps"]
+(MLS_RECORDS, MLS_READS, MLS_WRITES, MLS_L1_HITS, MLS_L1_LATENCY_PS, MLS_L2_HITS, MLS_L2_LATENCY_PS, MLS_L2_MISSES,
+ MLS_L2_MISS_LATENCY_PS, MLS_MAX_LATENCY_PS) = range(10)
+MLS_TYPE_COUNTS = 10     # + instruction type: totals over the tiles (mem_synthetic_run)
+MLS_MAX_TILE_CLOCK_PS = 16
+MLS_HIST = 18            # + bit length of the latency in ps, 65 bins
+NUM_MLS = MLS_HIST + 65
+
+
+class MemTrafficParams(ctypes.Structure):
+    """gg_mem_traffic_params: the eleven numbers of a synthetic_memory input
+    file, the seed of tile 0's streams and the srandom() seed of the address
+    map.  Defaults = inputs/input.64."""
+    _fields_ = [("num_threads", ctypes.c_uint32), ("degree_of_sharing", ctypes.c_uint32),
+                ("num_shared_addresses", ctypes.c_uint32), ("num_private_addresses", ctypes.c_uint32),
+                ("instructions_per_tile", ctypes.c_uint64), ("probability", ctypes.c_float * NUM_MEM_INS_TYPES),
+                ("seed_base", ctypes.c_uint64), ("map_seed", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+    def __init__(self, num_threads=64, degree_of_sharing=1, num_shared_addresses=1024, num_private_addresses=256,
+                 instructions_per_tile=10000, probability=(0.7, 0.025, 0.060, 0.015, 0.14, 0.06), seed_base=0,
+                 map_seed=1):
+        if len(probability) != NUM_MEM_INS_TYPES:
+            raise ValueError("six probabilities expected")
+        super().__init__(num_threads, degree_of_sharing, num_shared_addresses, num_private_addresses,
+                         instructions_per_tile, (ctypes.c_float * NUM_MEM_INS_TYPES)(*probability), seed_base,
+                         map_seed, 0)
+
+    @classmethod
+    def from_input_file(cls, path, ns=None):
+        """The reference's input format: eleven whitespace-separated numbers
+        (synthetic_memory.cc:235-260); ns overrides the degree of sharing as
+        its -ns option does."""
+        tok = open(path).read().split()
+        if len(tok) < 11:
+            raise ValueError("%s: eleven numbers expected, found %d" % (path, len(tok)))
+        ints = [int(x) for x in tok[:5]]
+        if ns is not None:
+            ints[1] = int(ns)
+        return cls(*ints, probability=tuple(float(x) for x in tok[5:11]))
+
+    def replace(self, **kw):
+        """A copy with some fields changed (probability: a sequence of six)."""
+        d = dict(num_threads=self.num_threads, degree_of_sharing=self.degree_of_sharing,
+                 num_shared_addresses=self.num_shared_addresses, num_private_addresses=self.num_private_addresses,
+                 instructions_per_tile=self.instructions_per_tile, probability=tuple(self.probability),
+                 seed_base=self.seed_base, map_seed=self.map_seed)
+        for k in kw:
+            if k not in d:
+                raise KeyError(k)
+        d.update(kw)
+        return MemTrafficParams(**d)
+
+
 CMSG_DTYPE = None  # filled below (numpy view of gg_cmsg)
 NUM_NET_COUNTERS = len(NET_COUNTERS)
 

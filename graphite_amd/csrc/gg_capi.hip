@@ -222,6 +222,7 @@ void gg_destroy(gg_ctx* ctx)
   gg_coh_free(ctx);
   gg_stats_free(ctx);
   gg_synth_free(ctx);
+  gg_memsynth_free(ctx);
   if (ctx->round && ctx->round_free) ctx->round_free(ctx->round);
   for (gg_timer& t : ctx->timers) { hipEventDestroy(t.start); hipEventDestroy(t.stop); }
   delete ctx;             // the context's own arrays: its arena and buffers (gg_devmem.h)

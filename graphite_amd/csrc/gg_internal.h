@@ -85,6 +85,7 @@ struct gg_coh_state;
 struct gg_stats_state;
 struct gg_atac_state;
 struct gg_synth_state;
+struct gg_memsynth_state;
 
 struct gg_ctx {
   gg_config cfg;
@@ -146,6 +147,8 @@ struct gg_ctx {
   gg_stats_state* stats = nullptr;
   // packet arrays of gg_noc_synthetic_run (gg_noc_synth.hip), allocated on first use
   gg_synth_state* synth = nullptr;
+  // trace and results of gg_mem_synthetic_run (gg_mem_synth.hip), allocated on first use
+  gg_memsynth_state* memsynth = nullptr;
 };
 inline void* gg_round_state(gg_ctx* ctx) { return ctx->round; }
 inline void gg_round_state_set(gg_ctx* ctx, void* p, void (*f)(void*)) { ctx->round = p; ctx->round_free = f; }
@@ -223,3 +226,5 @@ uint64_t  gg_coh_generation(gg_ctx* ctx);    // bumped by every gg_coherent_begi
 bool      gg_coh_windowed(const gg_ctx* ctx); // the begun run is fed its trace in windows (gg_coherent_begin_window)
 // synthetic network traffic (gg_noc_synth.hip)
 void      gg_synth_free(gg_ctx* ctx);
+// synthetic memory traffic (gg_mem_synth.hip)
+void      gg_memsynth_free(gg_ctx* ctx);

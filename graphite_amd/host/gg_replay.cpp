@@ -58,6 +58,13 @@
 //       --load takes a comma-separated list: one such block per load, each on
 //       a context of its own; unless M is atac the list runs in one
 //       gg_noc_synthetic_run_many call
+//   gg_replay --coherent [--net M] [--protocol P] --synthetic-memory INPUTFILE [-ns K] [--tiles T]
+//       the reference's coherent-memory benchmark (synthetic_memory.cc < INPUTFILE
+//       [-ns K]) generated, run and reduced on the device (gg_mem_synthetic_run)
+//       on as many tiles as the file names threads (--tiles T: on T tiles): the
+//       executed instruction types of every tile and "Max Tile Clock" as the
+//       benchmark prints them, then one line of the reduction (accesses, hits
+//       and mean latency by level, max latency)
 //   gg_replay --summary-selftest
 //       prints writeCacheSummary() for fixed counters (no GPU needed)
 //   gg_replay --mosi-summary FILE TILES
@@ -102,14 +109,16 @@ int main(int argc, char** argv)
   uint32_t protocol = GG_PROTO_MSI;
   int ranks = 1, rank = 0;
   uint32_t shards = 1;
-  std::string synth_pattern;
+  std::string synth_pattern, mem_input;
+  long mem_ns = -1;
+  bool tiles_given = false;
   gg_traffic_params synth;
   std::vector<double> synth_loads;       // --load: one offered load per point
   gg_traffic_params_default(&synth);
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() -> const char* { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
-    if (a == "--tiles") tiles = (uint32_t)std::strtoul(next(), nullptr, 0);
+    if (a == "--tiles") { tiles = (uint32_t)std::strtoul(next(), nullptr, 0); tiles_given = true; }
     else if (a == "--per-tile") per_tile = std::strtoull(next(), nullptr, 0);
     else if (a == "--lines-log2") lines_log2 = (uint32_t)std::strtoul(next(), nullptr, 0);
     else if (a == "--batches") batches = (uint32_t)std::strtoul(next(), nullptr, 0);
@@ -184,6 +193,8 @@ int main(int argc, char** argv)
       return 0;
     }
     else if (a == "--synthetic-network") synth_pattern = next();
+    else if (a == "--synthetic-memory") mem_input = next();
+    else if (a == "-ns") mem_ns = std::strtol(next(), nullptr, 0);
     else if (a == "--load") {
       synth_loads.clear();
       for (const char* q = next();;) {
@@ -301,6 +312,28 @@ int main(int argc, char** argv)
                               cfg.net_model == GG_NET_EMESH_HOP_BY_HOP);
         writeLatencyStats(std::cout, &stats[i * GG_NUM_NLS]);
       }
+    } catch (const std::exception& e) {
+      std::fprintf(stderr, "gg_replay: %s\n", e.what());
+      return 1;
+    }
+    return 0;
+  }
+  if (!mem_input.empty()) {
+    if (!coherent) { std::fprintf(stderr, "gg_replay: --synthetic-memory is a --coherent run\n"); return 2; }
+    try {
+      gg_mem_traffic_params mp = readMemTrafficInput(mem_input, mem_ns);
+      if (tiles_given) mp.num_threads = tiles;
+      gg_config cfg;
+      gg_config_default(&cfg, mp.num_threads);
+      cfg.l2_assoc = l2_assoc;
+      cfg.net_model = net;
+      cfg.protocol = protocol;
+      Backend be(cfg);
+      SyntheticMemory sm(be);
+      const std::vector<uint64_t> stats = sm.run(mp);
+      writeMemTypeCounts(std::cout, sm.typeCounts(cfg.num_tiles).data(), cfg.num_tiles);
+      writeMaxTileClock(std::cout, stats.data());
+      writeMemLatencyStats(std::cout, stats.data());
     } catch (const std::exception& e) {
       std::fprintf(stderr, "gg_replay: %s\n", e.what());
       return 1;

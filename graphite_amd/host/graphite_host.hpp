@@ -1017,4 +1017,74 @@ class SyntheticNetwork {
   Backend& _be;
 };
 
+// A synthetic_memory input file (synthetic_memory.cc:235-260): eleven numbers;
+// ns >= 0 overrides the degree of sharing as the benchmark's -ns does.
+inline gg_mem_traffic_params readMemTrafficInput(const std::string& path, long ns = -1)
+{
+  std::ifstream f(path);
+  gg_mem_traffic_params p;
+  gg_mem_traffic_params_default(&p);
+  uint64_t v[5];
+  for (uint64_t& x : v) f >> x;
+  for (float& x : p.probability) f >> x;
+  if (!f) throw std::invalid_argument("cannot read eleven numbers from " + path);
+  p.num_threads = (uint32_t)v[0];
+  p.degree_of_sharing = ns >= 0 ? (uint32_t)ns : (uint32_t)v[1];
+  p.num_shared_addresses = (uint32_t)v[2];
+  p.num_private_addresses = (uint32_t)v[3];
+  p.instructions_per_tile = v[4];
+  return p;
+}
+
+// The benchmark's own output (synthetic_memory.cc:129, :303-308): the executed
+// instruction types of every tile and the max tile clock in ns.
+inline void writeMemTypeCounts(std::ostream& out, const uint64_t* counts, uint32_t tiles)
+{
+  for (uint32_t t = 0; t < tiles; ++t) {
+    out << "thread(" << t << ") -> ";
+    for (int k = 0; k < GG_NUM_MEM_INS_TYPES; ++k) out << counts[(size_t)t * GG_NUM_MEM_INS_TYPES + k] << "\t";
+    out << "\n";
+  }
+}
+inline void writeMaxTileClock(std::ostream& out, const uint64_t* s)
+{
+  out << "Success: Max Tile Clock(" << psToNanosec(s[GG_MLS_MAX_TILE_CLOCK_PS]) << " ns)" << std::endl;
+}
+// One line of gg_mem_latency_stats' words: accesses, where they were served
+// and the mean latency there, the maximum latency.
+inline void writeMemLatencyStats(std::ostream& out, const uint64_t* s)
+{
+  auto mean = [](uint64_t sum, uint64_t n) { return n ? (double)sum / (double)n : 0.0; };
+  std::ostringstream os;                 // (the caller's stream keeps its format flags)
+  os << "Synthetic Memory: accesses " << s[GG_MLS_RECORDS] << " reads " << s[GG_MLS_READS] << " writes "
+     << s[GG_MLS_WRITES] << std::fixed << std::setprecision(3) << " L1 hits " << s[GG_MLS_L1_HITS] << " mean (ps) "
+     << mean(s[GG_MLS_L1_LATENCY_PS], s[GG_MLS_L1_HITS]) << " L2 hits " << s[GG_MLS_L2_HITS] << " mean (ps) "
+     << mean(s[GG_MLS_L2_LATENCY_PS], s[GG_MLS_L2_HITS]) << " L2 misses " << s[GG_MLS_L2_MISSES] << " mean (ps) "
+     << mean(s[GG_MLS_L2_MISS_LATENCY_PS], s[GG_MLS_L2_MISSES]) << " max latency (ps) " << s[GG_MLS_MAX_LATENCY_PS];
+  out << os.str() << std::endl;
+}
+
+// The benchmark on a context: generate, run, reduce (gg_mem_synthetic_run).
+class SyntheticMemory {
+ public:
+  explicit SyntheticMemory(Backend& be) : _be(be) {}
+  std::vector<uint64_t> run(const gg_mem_traffic_params& p, hipStream_t stream = nullptr)
+  {
+    std::vector<uint64_t> s(GG_NUM_MLS);
+    check(gg_mem_synthetic_run(_be.ctx(), &p, s.data(), stream), "gg_mem_synthetic_run");
+    return s;
+  }
+  // [tiles][GG_NUM_MEM_INS_TYPES] of the last run
+  std::vector<uint64_t> typeCounts(uint32_t tiles)
+  {
+    const uint64_t* dev = nullptr;
+    check(gg_mem_synthetic_get(_be.ctx(), nullptr, nullptr, nullptr, &dev), "gg_mem_synthetic_get");
+    std::vector<uint64_t> c((size_t)tiles * GG_NUM_MEM_INS_TYPES);
+    hip_check(hipMemcpy(c.data(), dev, c.size() * sizeof(uint64_t), hipMemcpyDeviceToHost), "hipMemcpy");
+    return c;
+  }
+ private:
+  Backend& _be;
+};
+
 }  // namespace graphite_amd

@@ -44,6 +44,11 @@
  *   gg_noc_synthetic_run       the benchmark in one call on a context
  *   gg_noc_route_batch_many    many independent batches, each on its own context,
  *   gg_noc_synthetic_run_many  in one set of launches (a load-latency sweep)
+ *   gg_gen_memory_traffic      the instruction stream of
+ *                              tests/benchmarks/synthetic_memory/synthetic_memory.cc:135-399
+ *                              as a coherent trace
+ *   gg_mem_latency_stats       accesses, levels and latency of a coherent run
+ *   gg_mem_synthetic_run       the benchmark in one call on a context
  *
  * Conventions: every function returns a gg_status (0 = OK, negative = error);
  * no exception crosses the ABI; pointers named *_dev are HIP device pointers,
@@ -1081,6 +1086,128 @@ gg_status gg_noc_route_batch_many(gg_ctx* const* ctxs, uint32_t n, const gg_pack
 gg_status gg_noc_synthetic_run_many(gg_ctx* const* ctxs, uint32_t n, const gg_traffic_params* params,
                                     uint64_t* stats /* host, n * GG_NUM_NLS */,
                                     gg_status* statuses /* may be NULL */, void* stream);
+
+/* Synthetic memory traffic: the instruction stream of the
+ * reference's tests/benchmarks/synthetic_memory/synthetic_memory.cc as a
+ * gg_trace that every coherent driver takes.  The benchmark seeds every Random
+ * with the tile id and the address map with srandom(1), and its stream depends
+ * on no simulated time, so a run is a function of its input file and the trace
+ * is generated up front, bit for bit.
+ *  - Input (:235-260): the eleven numbers of an input file; -ns overrides
+ *    degree_of_sharing.  probability[]: NON_MEMORY, RD_ONLY_SHARED_READ,
+ *    RD_WR_SHARED_READ, RD_WR_SHARED_WRITE, PRIVATE_READ, PRIVATE_WRITE.
+ *    num_threads is the file's first number: 0 or the tile count of the call,
+ *    else GG_ERR_INVALID.  T below is the tile count of the call.
+ *  - Derived (:266-272): frac_ro = p[1] / (p[1] + p[2] + p[3]) in float; the
+ *    cumulative probabilities by sequential float adds.
+ *  - Address map (:314-334): srandom(map_seed); for shared address i in order
+ *    and j < degree, tid = (int)((((float)random()) / RAND_MAX) * T) in float;
+ *    line i goes on tid's read-only list if i < (int)(frac_ro * num_shared),
+ *    else on its read-write list.  Duplicates stay, list order is push order.
+ *    Drawn with random_r on a state of its own: random()'s state is untouched.
+ *  - Per tile t (:285-296): three drand48_r streams (X' = (0x5DEECE66D X + 0xB)
+ *    mod 2^48, X0 = (seed << 16) | 0x330E, u = X' 2^-48), all seeded with
+ *    seed_base + t (its low 32 bits, as srand48_r keeps them): instruction
+ *    type, read-only index, read-write index.
+ *  - Per instruction (:143-228, :357-399): the type is the first i with
+ *    (float)u < cum[i].  NON_MEMORY costs one cycle (the gap of the tile's
+ *    next record).  A shared type whose list is empty on the tile does
+ *    nothing: no draw, no time, no record.  Otherwise the address is list[(int)
+ *    (u * size)] from the matching stream (reads and writes of read-write data
+ *    share one).  Private access k of the tile (reads and writes counted
+ *    together) goes to (1 << (log2(num_shared) + log2(line))) + ((t *
+ *    num_private + k mod num_private) << log2(line)).  Every access is 4 bytes
+ *    at a line-aligned address: one record.
+ * Departures from the reference.  (1) It reads the key
+ * l1_dcache/T1/cache_block_size, which no configuration has, and so shifts by
+ * floorLog2(0) = -1; here the line size is line_bytes.  (2) frac_ro with a zero
+ * denominator is 0.  (3) The final CarbonBarrierWait is left out: a BARRIER
+ * record carries no gap, so the tile's trailing non-memory cycles could not
+ * precede it, and the reported clock does not depend on it.                   */
+enum { GG_MI_NON_MEMORY = 0, GG_MI_RD_ONLY_SHARED_READ, GG_MI_RD_WR_SHARED_READ, GG_MI_RD_WR_SHARED_WRITE,
+       GG_MI_PRIVATE_READ, GG_MI_PRIVATE_WRITE, GG_NUM_MEM_INS_TYPES };
+typedef struct gg_mem_traffic_params {
+  uint32_t num_threads;            /* the file's thread count: 0, or the tile count of the call */
+  uint32_t degree_of_sharing;      /* tiles drawn per shared address           (-ns) */
+  uint32_t num_shared_addresses;   /* lines, a power of two                          */
+  uint32_t num_private_addresses;  /* lines per tile, a power of two (or 0: none)    */
+  uint64_t instructions_per_tile;  /* N                                              */
+  float    probability[GG_NUM_MEM_INS_TYPES];
+  uint64_t seed_base;              /* tile t seeds its three streams with seed_base + t; the reference: 0 */
+  uint32_t map_seed;               /* srandom() seed of the address map; the reference: 1 */
+  uint32_t reserved;               /* 0 */
+} gg_mem_traffic_params;
+/* The values of inputs/input.64: 64 threads, degree 1, 1024 shared and 256
+ * private lines, 10000 instructions, 0.7 / 0.025 / 0.06 / 0.015 / 0.14 / 0.06,
+ * seed_base 0, map_seed 1.                                                   */
+void      gg_mem_traffic_params_default(gg_mem_traffic_params* p);
+/* One function, called twice, because a tile's record count is only known
+ * after a pass over its instructions.
+ *  - Plan: addr_dev == NULL and meta_dev == NULL.  Draws the map, runs the
+ *    count pass and writes tile_offsets[num_tiles + 1] (host) and *num_records.
+ *  - Fill: addr_dev and meta_dev hold `capacity` records, capacity >= the
+ *    plan's total (else GG_ERR_INVALID).  Repeats the plan (it keeps no state
+ *    between calls; the count pass reads no memory but the lists) and writes
+ *    addr_dev, meta_dev (WRITE bit; gap in bits 1..30 = NON_MEMORY instructions
+ *    since the tile's previous access), tail_cycles_dev[T] (NON_MEMORY
+ *    instructions after the tile's last access; u64) and type_counts_dev[T][6]
+ *    (u64; every instruction counted, the skipped ones included).  The last
+ *    two may be NULL, as may tile_offsets and num_records.
+ * GG_ERR_INVALID: NULL p, one of addr_dev / meta_dev NULL, num_tiles == 0,
+ * num_shared not a power of two (0 included), num_private not a power of two
+ * and not 0, num_private == 0 with p[4] + p[5] > 0, degree > T, a probability
+ * outside [0, 1] or not finite, N == 0, line_bytes not a power of two.
+ * GG_ERR_RANGE: log2(num_shared) + log2(line) > 30 (the reference shifts an
+ * int), T * num_private >= 2^31, N >= 2^31; and two limits of this
+ * implementation: num_shared * degree >= 2^31 map entries, and (after the count
+ * pass) a tile with 2^30 NON_MEMORY instructions or more, whose gap might not
+ * fit 30 bits.  GG_ERR_STATE, where the reference
+ * would assert or index out of range: a map draw gives tid == T ((float)
+ * random() can round to 2^31); a tile draws from a list of more than 32768
+ * entries; a type draw with (float)u >= cum[5] — found by the count pass and
+ * reported after it, gg_last_error naming the lowest (tile, instruction).  All
+ * but the last two before any launch.  Synchronizes the stream.            */
+gg_status gg_gen_memory_traffic(const gg_mem_traffic_params* p, uint32_t num_tiles, uint32_t line_bytes,
+                                uint64_t* tile_offsets /* host, num_tiles + 1; may be NULL */,
+                                uint64_t* num_records /* may be NULL */,
+                                uint64_t* addr_dev, uint32_t* meta_dev, uint64_t capacity,
+                                uint64_t* tail_cycles_dev /* [tiles], may be NULL */,
+                                uint64_t* type_counts_dev /* [tiles][6], may be NULL */, void* stream);
+/* One pass over the access words (latency_ps << 2) | level of any coherent run
+ * of trace (its meta_dev and num_records are read; tile_offsets is not).  A
+ * BARRIER record is skipped; a GG_META_CONT record counts as an access of its
+ * own line.  stats: host, GG_NUM_MLS words; words GG_MLS_TYPE_COUNTS ..
+ * GG_MLS_HIST - 1 are 0.  Synchronizes the stream.                           */
+enum { GG_MLS_RECORDS = 0, GG_MLS_READS, GG_MLS_WRITES,
+       GG_MLS_L1_HITS, GG_MLS_L1_LATENCY_PS, GG_MLS_L2_HITS, GG_MLS_L2_LATENCY_PS,
+       GG_MLS_L2_MISSES, GG_MLS_L2_MISS_LATENCY_PS, GG_MLS_MAX_LATENCY_PS,
+       GG_MLS_TYPE_COUNTS = 10 /* + GG_MI_*: instructions of each type over all tiles (gg_mem_synthetic_run) */,
+       GG_MLS_MAX_TILE_CLOCK_PS = 16 /* the benchmark's "Max Tile Clock" (gg_mem_synthetic_run) */,
+       GG_MLS_HIST = 18 /* + bit length of latency_ps: 0 for 0, else 64 - clz; 65 bins */,
+       GG_NUM_MLS = GG_MLS_HIST + 65 };
+gg_status gg_mem_latency_stats(const gg_trace* trace, const uint64_t* access_out_dev,
+                               uint64_t* stats /* host, GG_NUM_MLS */, void* stream);
+/* The benchmark in one call: generates p's trace for cfg.num_tiles tiles and
+ * the context's line size, runs it with gg_coherent_run and reduces the access
+ * words.  Beyond the words of gg_mem_latency_stats: the total of each
+ * instruction type, and GG_MLS_MAX_TILE_CLOCK_PS = max over tiles of
+ * GG_CT_CLOCK_PS[t] + tail[t] * Latency(1, frequency) (:114-129).  The trace,
+ * the access words, the tails and the counts are scratch of the context, grown
+ * on demand and freed by gg_destroy.  Errors: those of gg_gen_memory_traffic
+ * and gg_coherent_run; an ATAC context GG_ERR_UNSUPPORTED.  Synchronizes.    */
+gg_status gg_mem_synthetic_run(gg_ctx* ctx, const gg_mem_traffic_params* p, uint64_t* stats /* host, GG_NUM_MLS */,
+                               void* stream);
+/* The arrays of the context's last gg_mem_synthetic_run, valid until its next
+ * one or gg_destroy: the trace (tile_offsets owned by the context) to hand to
+ * another driver, and the device arrays of the access words, tails [T] and
+ * type counts [T][6] (each may be NULL).  GG_ERR_INVALID without such a run. */
+gg_status gg_mem_synthetic_get(gg_ctx* ctx, gg_trace* trace, const uint64_t** access_out_dev,
+                               const uint64_t** tail_cycles_dev, const uint64_t** type_counts_dev);
+/* The same arrays copied into the caller's device buffers (num_records, T and
+ * T * 6 entries; each may be NULL), for a caller that keeps them past the
+ * context's next run.  Synchronizes the stream.                             */
+gg_status gg_mem_synthetic_copy(gg_ctx* ctx, uint64_t* addr_dev, uint32_t* meta_dev, uint64_t* access_out_dev,
+                                uint64_t* tail_cycles_dev, uint64_t* type_counts_dev, void* stream);
 
 /* Multi-line accesses (replaces the line loop of Core::initiateMemoryAccess,
  * common/tile/core/core.cc:139-266, for the coherent mode).  Input: a
