@@ -68,6 +68,8 @@ EXPORTS = ["gg_abi_version", "gg_last_error", "gg_config_default", "gg_create", 
            "gg_coherent_advance", "gg_coherent_snapshot_size", "gg_coherent_snapshot", "gg_coherent_restore",
            "gg_coherent_advance_many",
            "gg_coherent_begin_window", "gg_coherent_next_window", "gg_coherent_window_state",
+           "gg_coherent_window_snapshot_size", "gg_coherent_window_snapshot", "gg_coherent_window_restore",
+           "gg_window_snapshot_state",
            "gg_traffic_params_default", "gg_gen_network_traffic", "gg_noc_latency_stats", "gg_noc_synthetic_run",
            "gg_noc_route_batch_many", "gg_noc_synthetic_run_many",
            "gg_mem_traffic_params_default", "gg_gen_memory_traffic", "gg_mem_latency_stats", "gg_mem_synthetic_run",
@@ -211,7 +213,13 @@ def load():
     L.gg_coherent_begin_window.argtypes = [vp, ctypes.POINTER(_Trace), vp, vp, vp]
     L.gg_coherent_next_window.argtypes = [vp, ctypes.POINTER(_Trace), vp, vp, vp]
     L.gg_coherent_window_state.argtypes = [vp, vp, vp]
-    for name in ["gg_coherent_begin_window", "gg_coherent_next_window", "gg_coherent_window_state"]:
+    L.gg_coherent_window_snapshot_size.argtypes = [vp, ctypes.POINTER(u64)]
+    L.gg_coherent_window_snapshot.argtypes = [vp, vp, u64, ctypes.POINTER(u64)]
+    L.gg_coherent_window_restore.argtypes = [vp, ctypes.POINTER(_Trace), vp, vp, vp, u64, vp]
+    L.gg_window_snapshot_state.argtypes = [vp, u64, u32, vp, vp]
+    for name in ["gg_coherent_begin_window", "gg_coherent_next_window", "gg_coherent_window_state",
+                 "gg_coherent_window_snapshot_size", "gg_coherent_window_snapshot", "gg_coherent_window_restore",
+                 "gg_window_snapshot_state"]:
         getattr(L, name).restype = i32
     L.gg_traffic_params_default.argtypes = [ctypes.POINTER(TrafficParams)]
     L.gg_traffic_params_default.restype = None
@@ -584,6 +592,39 @@ class Backend:
         _check(load().gg_coherent_window_state(self.h, c.ctypes.data_as(ctypes.c_void_p), m.ctypes.data_as(ctypes.c_void_p)))
         return c, m
 
+    # ---- a windowed run in legs (gg_coherent_window_snapshot / _window_restore)
+    def coherent_window_snapshot_size(self):
+        n = ctypes.c_uint64(0)
+        _check(load().gg_coherent_window_snapshot_size(self.h, ctypes.byref(n)))
+        return n.value
+
+    def coherent_window_snapshot(self, cap=None):
+        """coherent_snapshot for a run fed in windows, at its clean point (after
+        coherent_begin_window, a returned coherent_advance, coherent_next_window
+        or coherent_window_restore): the same container plus a `win` section.
+        The bytes do not depend on where the windows were cut."""
+        n = ctypes.c_uint64(self.coherent_window_snapshot_size() if cap is None else cap)
+        buf = np.empty(max(n.value, 1), np.uint8)
+        got = ctypes.c_uint64(0)
+        rc = load().gg_coherent_window_snapshot(self.h, buf.ctypes.data_as(ctypes.c_void_p), n.value, ctypes.byref(got))
+        if rc != GG_OK:
+            e = GGError(rc, load().gg_last_error().decode(errors="replace"))
+            e.needed = got.value         # GG_ERR_RANGE: the bytes a snapshot needs
+            raise e
+        return buf[:got.value]
+
+    def coherent_window_restore(self, addr, meta, tile_offsets, out=None, final_tiles=None, blob=None, stream=None):
+        """Reset as coherent_begin does, put a windowed snapshot's state back and
+        install the windows as coherent_next_window would: tile t's records
+        begin at record consumed[t] of its trace (window_snapshot_state(blob)).
+        The run continues with coherent_advance and coherent_next_window."""
+        if blob is None:
+            raise ValueError("coherent_window_restore needs the snapshot (blob=...)")
+        b = np.ascontiguousarray(np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray)) else blob, np.uint8)
+        fn = lambda h, tr, out_p, fin_p, st: load().gg_coherent_window_restore(
+            h, tr, out_p, fin_p, b.ctypes.data_as(ctypes.c_void_p), b.size, st)
+        self._window(fn, addr, meta, tile_offsets, out, final_tiles, stream)
+
     def round_pack(self, world, rank, q):
         """gg_round_pack: quantum q's steps + the tail on the context's stream;
         returns the RoundIO with the device slots / words to move.  The
@@ -814,6 +855,17 @@ def coherent_advance_many(backends, stops=None, stream=None):
         e.results = results
         raise e
     return results
+
+
+def window_snapshot_state(blob, num_tiles):
+    """(consumed, finished) of a windowed run's snapshot
+    (gg_window_snapshot_state): uint64 / bool [num_tiles].  No backend and no
+    device: a fresh process cuts its first windows from the snapshot alone."""
+    b = np.ascontiguousarray(np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray)) else blob, np.uint8)
+    c, f = np.zeros(max(num_tiles, 1), np.uint64), np.zeros(max(num_tiles, 1), np.uint8)
+    _check(load().gg_window_snapshot_state(b.ctypes.data_as(ctypes.c_void_p), b.size, num_tiles,
+                                           c.ctypes.data_as(ctypes.c_void_p), f.ctypes.data_as(ctypes.c_void_p)))
+    return c[:num_tiles], f[:num_tiles].astype(bool)
 
 
 def noc_route_batch_many(backends, batches, outs, stream=None):

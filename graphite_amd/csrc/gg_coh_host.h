@@ -32,6 +32,10 @@ struct gg_coh_state {
   uint8_t* win_fin_dev = nullptr;
   uint32_t* win_bad_dev = nullptr;
   uint64_t* win_state_dev = nullptr;
+  // a windowed run's snapshot (gg_coherent_window_snapshot / _window_restore):
+  // the win records [T] on the device, the canonical copy of S.ts [L]
+  uint64_t* win_rec_dev = nullptr;
+  ggc::TileSt* win_ts_dev = nullptr;
   // who drives the begun run: nobody yet, the device loop (gg_coherent_run /
   // _advance) or the host (gg_coherent_quantum, the round) — they keep
   // different state words, so one run takes one of them
@@ -92,6 +96,17 @@ gg_status coh_owns_all(const gg_ctx* ctx, gg_status code, const char* what);
 // a whole trace's or a window's offsets and pointers against T tiles; what: the messages' prefix, or null
 gg_status coh_trace_check(const gg_trace* tr, uint32_t T, const char* what);
 gg_status coh_window_exhausted();                       // gg_coh_window.hip
+// A windowed run's snapshot and restore, the parts on the device (gg_coh_window.hip).
+// gather: the tiles' win records (by tile number, ggsnap::WinRec words) and
+// S.ts in canonical form (rec = consumed count, rec_end = 0) onto the host;
+// the run's state is only read.  restore_check: win's ranges against the
+// records of a snapshot (host, [T]), before anything is changed.
+// restore_install: after the reset and the state are in place, the tiles onto
+// win's arrays as gg_coherent_next_window would; the run is windowed after it.
+gg_status coh_window_gather(gg_ctx* ctx, std::vector<ggc::TileSt>& ts, std::vector<uint64_t>& recs);
+gg_status coh_window_restore_check(gg_ctx* ctx, const char* what, const gg_trace* win, const uint8_t* final_tiles,
+                                   const uint8_t* recs, hipStream_t s);
+gg_status coh_window_restore_install(gg_ctx* ctx, const gg_trace* win, hipStream_t s);
 gg_status coh_deadlocked(int instance = -1);            // QS_DONE == 2 (instance: of an ensemble)
 // A leg of the device loop (gg_coherent_advance, _advance_many).  look: the
 // run's stream synchronised, its quantum words in qs[QS_N], *next_quantum and

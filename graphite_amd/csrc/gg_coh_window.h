@@ -25,4 +25,17 @@ void launch_window_install(const CP& P, const CS& S, const uint64_t* addr, const
 // consumed [T] and min_records [T] (device; zeros for tiles not owned)
 void launch_window_state(const CP& P, const CS& S, uint64_t* consumed, uint64_t* min_records, hipStream_t s);
 
+// A windowed run's snapshot (gg_coherent_window_snapshot).  recs [T][4]: a
+// tile's {consumed, finished, addr, meta of the record it stands on} by tile
+// number (ggsnap::WinRec); ts_out [L]: S.ts with rec = consumed and rec_end =
+// 0.  The run's own state is read, never written.
+void launch_window_gather(const CP& P, const CS& S, TileSt* ts_out, uint64_t* recs, hipStream_t s);
+// Its restore (gg_coherent_window_restore); recs as above, from the snapshot.
+// phase 0, before anything is changed: win's ranges against recs, the verdict
+// in bad[] as mode 1 leaves it (no tile state is read).  phase 1, once the
+// reset and the snapshot's arrays are in place (S.ts canonical, S.win bound,
+// its header ~0): rec / rec_end onto win's arrays, the WN_* words, the horizon.
+void launch_window_restore(const CP& P, const CS& S, const uint64_t* addr, const uint32_t* meta, const uint64_t* offs,
+                           const uint8_t* fin, const uint64_t* recs, int phase, uint32_t* bad, hipStream_t s);
+
 }  // namespace ggc

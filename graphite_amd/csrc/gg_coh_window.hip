@@ -74,6 +74,67 @@ __global__ void __launch_bounds__(256) k_c_window_state(CP P, CS S, uint64_t* co
   min_records[tile] = need;
 }
 
+// A windowed run's snapshot: what of a tile's state is relative to the bound
+// window leaves in a form that is not — the position as the count of consumed
+// records, the record the tile stands on by value.  Into staging only.
+__global__ void __launch_bounds__(256) k_c_window_gather(CP P, CS S, TileSt* ts_out, uint64_t* recs)
+{
+  const uint32_t lt = blockIdx.x * blockDim.x + threadIdx.x;
+  if (lt >= P.L) return;
+  const uint32_t tile = S.gtile[lt];
+  const uint64_t* w = (const uint64_t*)S.win + WN_HDR + (size_t)lt * WN_TILE;
+  TileSt t = *((const TileSt*)S.ts + lt);
+  const uint64_t consumed = w[WN_CBASE] + (t.rec - w[WN_FIRST]);
+  const bool fin = t.rec >= t.rec_end;                 // (of a final tile: the host has refused a failed run)
+  uint64_t* o = recs + (size_t)tile * 4;
+  o[0] = consumed; o[1] = fin ? 1ull : 0ull;
+  o[2] = fin ? 0ull : S.addr[t.rec]; o[3] = fin ? 0ull : (uint64_t)S.meta[t.rec];
+  t.rec = consumed; t.rec_end = 0;
+  ts_out[lt] = t;
+}
+
+// Its restore.  Phase 0 reads the new windows and the snapshot's records
+// alone; phase 1 is mode 2 of the hand-over with the consumed count from the
+// snapshot (S.ts[lt].rec holds the same count, clk the tile's clock).
+__global__ void __launch_bounds__(256) k_c_window_restore(CP P, CS S, const uint64_t* addr, const uint32_t* meta,
+                                                          const uint64_t* offs, const uint8_t* fin, const uint64_t* recs,
+                                                          int phase, uint32_t* bad)
+{
+  const uint32_t lt = blockIdx.x * blockDim.x + threadIdx.x;
+  if (lt >= P.L) return;
+  const uint32_t tile = S.gtile[lt];
+  const uint64_t ns = offs[tile], ne = offs[tile + 1];
+  const uint64_t nf = fin && fin[tile] ? 1ull : 0ull;
+  const uint64_t* r = recs + (size_t)tile * 4;
+  if (phase == 0) {
+    uint32_t b = 0;
+    if (r[1]) b = ne != ns ? WB_FINISHED : !nf ? WB_FINAL : 0u;
+    else if (ne == ns) b = WB_EMPTY;
+    else if (addr[ns] != r[2] || (uint64_t)meta[ns] != r[3]) b = WB_RECORD;
+    if (b) { atomicOr(&bad[0], b); atomicMin(&bad[1], tile + 1); }
+    return;
+  }
+  uint64_t* w = (uint64_t*)S.win + WN_HDR + (size_t)lt * WN_TILE;
+  TileSt* ts = (TileSt*)S.ts + lt;
+  w[WN_FINAL] = nf; w[WN_CBASE] = r[0]; w[WN_FIRST] = ns;
+  ts->rec = ns; ts->rec_end = ne;
+  uint64_t g = ~0ull;
+  if (!nf) {
+    g = win_guard(meta, ns, ne);
+    atomicMin((unsigned long long*)&S.win[WN_HOR], (unsigned long long)win_horizon(P, ns, ts->clk, g));
+  }
+  w[WN_GUARD] = g;
+}
+
+void launch_window_gather(const CP& P, const CS& S, TileSt* ts_out, uint64_t* recs, hipStream_t s)
+{
+  hipLaunchKernelGGL(k_c_window_gather, dim3((P.L + 255) / 256), dim3(256), 0, s, P, S, ts_out, recs);
+}
+void launch_window_restore(const CP& P, const CS& S, const uint64_t* addr, const uint32_t* meta, const uint64_t* offs,
+                           const uint8_t* fin, const uint64_t* recs, int phase, uint32_t* bad, hipStream_t s)
+{
+  hipLaunchKernelGGL(k_c_window_restore, dim3((P.L + 255) / 256), dim3(256), 0, s, P, S, addr, meta, offs, fin, recs, phase, bad);
+}
 void launch_window_install(const CP& P, const CS& S, const uint64_t* addr, const uint32_t* meta, const uint64_t* offs,
                            const uint8_t* fin, int mode, uint32_t* bad, hipStream_t s)
 {
@@ -110,6 +171,8 @@ static gg_status win_upload(gg_ctx* ctx, const char* what, const gg_trace* win, 
     if (gg_status st = C->mem.alloc(&C->win_fin_dev, (uint64_t)T)) return st;
     if (gg_status st = C->mem.alloc(&C->win_bad_dev, 2)) return st;
     if (gg_status st = C->mem.alloc(&C->win_state_dev, 2 * (uint64_t)T)) return st;
+    if (gg_status st = C->mem.alloc(&C->win_rec_dev, 4 * (uint64_t)T)) return st;
+    if (gg_status st = C->mem.alloc(&C->win_ts_dev, (uint64_t)C->P.L)) return st;
   }
   // (offs_dev is read by k_c_reset at begin only: between begins it stages a window's offsets)
   GG_HIP(hipMemcpyAsync(C->offs_dev, win->tile_offsets, sizeof(uint64_t) * (T + 1), hipMemcpyHostToDevice, s));
@@ -220,5 +283,61 @@ gg_status gg_coherent_window_state(gg_ctx* ctx, uint64_t* consumed, uint64_t* mi
   GG_HIP(hipStreamSynchronize(s));
   if (consumed) GG_HIP(hipMemcpy(consumed, C->win_state_dev, sizeof(uint64_t) * T, hipMemcpyDeviceToHost));
   if (min_records) GG_HIP(hipMemcpy(min_records, C->win_state_dev + T, sizeof(uint64_t) * T, hipMemcpyDeviceToHost));
+  return GG_OK;
+}
+
+// ---- a windowed run's snapshot and restore: the device parts (host side: gg_snapshot.hip) ----
+gg_status coh_window_gather(gg_ctx* ctx, std::vector<TileSt>& ts, std::vector<uint64_t>& recs)
+{
+  gg_coh_state* C = ctx->coh;
+  hipStream_t s = ctx->last_stream;
+  const uint32_t T = C->P.T, L = C->P.L;
+  ts.resize(L); recs.resize((size_t)4 * T);
+  launch_window_gather(C->P, C->S, C->win_ts_dev, C->win_rec_dev, s);
+  GG_HIP(hipGetLastError());
+  GG_HIP(hipMemcpyAsync(ts.data(), C->win_ts_dev, sizeof(TileSt) * L, hipMemcpyDeviceToHost, s));
+  GG_HIP(hipMemcpyAsync(recs.data(), C->win_rec_dev, sizeof(uint64_t) * 4 * T, hipMemcpyDeviceToHost, s));
+  GG_HIP(hipStreamSynchronize(s));
+  return GG_OK;
+}
+
+gg_status coh_window_restore_check(gg_ctx* ctx, const char* what, const gg_trace* win, const uint8_t* final_tiles,
+                                   const uint8_t* recs, hipStream_t s)
+{
+  gg_coh_state* C = ctx->coh;
+  const uint32_t T = C->P.T;
+  if (gg_status st = win_upload(ctx, what, win, final_tiles, s)) return st;
+  GG_HIP(hipMemcpyAsync(C->win_rec_dev, recs, sizeof(uint64_t) * 4 * T, hipMemcpyHostToDevice, s));
+  launch_window_restore(C->P, C->S, win->addr_dev, win->meta_dev, C->offs_dev, C->win_fin_dev, C->win_rec_dev, 0,
+                        C->win_bad_dev, s);
+  GG_HIP(hipGetLastError());
+  uint32_t bad[2] = {0, 0};
+  GG_HIP(hipMemcpyAsync(bad, C->win_bad_dev, sizeof(bad), hipMemcpyDeviceToHost, s));
+  GG_HIP(hipStreamSynchronize(s));
+  if (bad[0]) {
+    const uint32_t t = bad[1] - 1;
+    const char* why = (bad[0] & WB_EMPTY)    ? "an unfinished tile's range holds no record"
+                    : (bad[0] & WB_RECORD)   ? "a window's first record is not the record its tile stood on (addr or meta)"
+                    : (bad[0] & WB_FINISHED) ? "a finished tile's range is not empty"
+                                             : "a tile that is not final has an empty window";
+    return gg_fail(GG_ERR_INVALID, "%s: %s (first at tile %u); nothing changed", what, why, t);
+  }
+  return GG_OK;
+}
+
+gg_status coh_window_restore_install(gg_ctx* ctx, const gg_trace* win, hipStream_t s)
+{
+  gg_coh_state* C = ctx->coh;
+  cs_set(C->S.win, C->win_dev);
+  const uint64_t w0[WN_HDR] = {~0ull, ~0ull};
+  GG_HIP(hipMemcpyAsync(C->win_dev, w0, sizeof(w0), hipMemcpyHostToDevice, s));
+  GG_HIP(hipMemcpyAsync(C->Sd, &C->S, sizeof(CS), hipMemcpyHostToDevice, s));
+  // (offs_dev holds win's offsets since the reset, win_fin_dev and win_rec_dev their values since the check)
+  launch_window_restore(C->P, C->S, win->addr_dev, win->meta_dev, C->offs_dev, C->win_fin_dev, C->win_rec_dev, 1,
+                        C->win_bad_dev, s);
+  GG_HIP(hipGetLastError());
+  GG_HIP(hipStreamSynchronize(s));
+  C->windowed = true;
+  C->drv = gg_coh_state::DRV_DEVICE;
   return GG_OK;
 }

@@ -12,6 +12,7 @@
 // address tables (~0 = empty) take the same three passes.
 #include "gg_coh_host.h"
 #include "gg_snapshot.h"
+#include "gg_snapshot_win.h"
 #include "gg_stats.h"
 
 #include <algorithm>
@@ -207,6 +208,27 @@ gg_status snap_valid(gg_ctx* ctx, const char* what)
                                    "clean point (after begin, an advance or a restore)", what);
   return GG_OK;
 }
+// the same for a run fed in windows (gg_coherent_window_snapshot): the clean
+// point is where a window may go in, or the end of the run
+gg_status snap_valid_win(gg_ctx* ctx, const char* what)
+{
+  GG_NOT_ATAC(ctx, what);
+  gg_coh_state* C = ctx->coh;
+  if (!C || !C->begun)
+    return gg_fail(GG_ERR_INVALID, "%s: gg_coherent_begin_window or gg_coherent_window_restore first", what);
+  if (!C->windowed)
+    return gg_fail(GG_ERR_INVALID, "%s: the run is not fed in windows: gg_coherent_snapshot takes its snapshot", what);
+  hipSetDevice(ctx->device);
+  GG_HIP(hipStreamSynchronize(ctx->last_stream));
+  uint64_t done = 0;
+  uint32_t err = 0;
+  GG_HIP(hipMemcpy(&done, C->S.qs + QS_DONE, sizeof(done), hipMemcpyDeviceToHost));
+  GG_HIP(hipMemcpy(&err, ctx->err_dev, sizeof(err), hipMemcpyDeviceToHost));
+  if (err || (done & 3) == 2)
+    return gg_fail(GG_ERR_INVALID, "%s: the run has failed%s: there is no state to continue from", what,
+                   (err & GG_DERR_WINDOW) ? " (window exhausted)" : "");
+  return GG_OK;
+}
 }  // namespace
 
 // The records live at a quantum boundary and the lists that hold them, on the
@@ -332,7 +354,11 @@ static gg_status snap_live(gg_coh_state* C, SnapCounts& n, SnapLive& v)
 }
 
 // host_buf == nullptr: the size only
-static gg_status coh_snapshot(gg_ctx* ctx, uint8_t* host_buf, uint64_t cap, uint64_t* bytes)
+// win: of a run fed in windows.  The tiles' positions leave as counts of
+// consumed records (S.ts from the gather kernel's canonical copy, the offsets
+// section as the prefix sums of the counts), the record each tile stands on
+// in the win section: no byte depends on where the windows were cut.
+static gg_status coh_snapshot(gg_ctx* ctx, uint8_t* host_buf, uint64_t cap, uint64_t* bytes, bool win)
 {
   gg_coh_state* C = ctx->coh;
   const CP& P = C->P; const CS& S = C->S;
@@ -362,7 +388,7 @@ static gg_status coh_snapshot(gg_ctx* ctx, uint8_t* host_buf, uint64_t cap, uint
   ggsnap::Layout lay;
   lay.add("cfg", ggsnap::SK_DENSE, 0, sizeof(gg_config), 0);
   lay.add("launch", ggsnap::SK_DENSE, 0, sizeof(SnapLaunch), 0);
-  lay.add("offsets", ggsnap::SK_DENSE, 0, sizeof(uint64_t) * C->offs_host.size(), 0);
+  lay.add("offsets", ggsnap::SK_DENSE, 0, sizeof(uint64_t) * (P.T + 1), 0);
   lay.add("stats", ggsnap::SK_DENSE, 0, sizeof(uint64_t) * stw.size(), 0);
   lay.add("err", ggsnap::SK_DENSE, 0, 2 * sizeof(uint32_t), 0);
   lay.add("noc_ctr", ggsnap::SK_DENSE, 0, sizeof(uint64_t) * P.T * GG_NUM_NET_COUNTERS, 0);
@@ -385,6 +411,8 @@ static gg_status coh_snapshot(gg_ctx* ctx, uint8_t* host_buf, uint64_t cap, uint
   const size_t first_pk = lay.sec.size();
   for (size_t i = 0; i < pk.size(); ++i)
     lay.add(pk[i].name, ggsnap::SK_PACKED, pk[i].src.rw * 8, base[i][P.L] * pk[i].src.rw * 8, base[i][P.L]);
+  const size_t win_sec = lay.sec.size();
+  if (win) lay.add(ggsnap::kWinSection, ggsnap::SK_DENSE, 0, sizeof(ggsnap::WinRec) * P.T, 0);
   const uint64_t total = lay.finish();
   *bytes = total;
   if (!host_buf) return GG_OK;
@@ -396,9 +424,18 @@ static gg_status coh_snapshot(gg_ctx* ctx, uint8_t* host_buf, uint64_t cap, uint
     if (nx > e) std::memset(host_buf + e, 0, nx - e);
   }
   auto at = [&](size_t i) { return host_buf + lay.sec[i].off; };
+  std::vector<TileSt> wts;
+  std::vector<uint64_t> wrec, offs(C->offs_host);
+  if (win) {
+    if (gg_status e = coh_window_gather(ctx, wts, wrec)) return e;
+    offs.assign((size_t)P.T + 1, 0);
+    for (uint32_t t = 0; t < P.T; ++t) offs[t + 1] = offs[t] + wrec[(size_t)4 * t];
+    std::memcpy(at(win_sec), wrec.data(), lay.sec[win_sec].bytes);
+  }
+  if (offs.size() != (size_t)P.T + 1) return gg_fail(GG_ERR_STATE, "snapshot: the bound trace's offsets");
   std::memcpy(at(0), &ctx->cfg, sizeof(gg_config));
   std::memcpy(at(1), &sl, sizeof(sl));
-  std::memcpy(at(2), C->offs_host.data(), lay.sec[2].bytes);
+  std::memcpy(at(2), offs.data(), lay.sec[2].bytes);
   std::memcpy(at(3), stw.data(), lay.sec[3].bytes);
   GG_HIP(hipMemcpy(at(4), ctx->err_dev, lay.sec[4].bytes, hipMemcpyDeviceToHost));
   GG_HIP(hipMemcpy(at(5), S.ctr, lay.sec[5].bytes, hipMemcpyDeviceToHost));
@@ -419,6 +456,7 @@ static gg_status coh_snapshot(gg_ctx* ctx, uint8_t* host_buf, uint64_t cap, uint
     from("xl", live.xl.data(), 8 * live.xl.size()); from("yl", live.yl.data(), 8 * live.yl.size());
     from("pool0", live.pool0.data(), sizeof(gg_cmsg) * live.pool0.size());
     from("pool1", live.pool1.data(), sizeof(gg_cmsg) * live.pool1.size());
+    if (win) from("ts", wts.data(), sizeof(TileSt) * wts.size());
     if (host) {
       if (hb != sec.bytes) return gg_fail(GG_ERR_STATE, "snapshot: section %s changed size while it was taken", a.name);
       if (hb) std::memcpy(at(si), host, hb);
@@ -431,6 +469,13 @@ static gg_status coh_snapshot(gg_ctx* ctx, uint8_t* host_buf, uint64_t cap, uint
     // the same bytes whoever drove the run.
     if (!std::strcmp(a.name, "qs")) std::memset(at(si) + sizeof(uint64_t) * QS_START, 0, sizeof(uint64_t));
     if (!std::strcmp(a.name, "ring")) std::memset(at(si) + sizeof(uint32_t) * 7, 0, sizeof(uint32_t) * 4);
+    // a pause for the next windows (kQsWindow) is a pause: whether the run
+    // stopped for them or for the caller's stop depends on the cuts
+    if (win && !std::strcmp(a.name, "qs")) {
+      uint64_t d;
+      std::memcpy(&d, at(si) + sizeof(uint64_t) * QS_DONE, sizeof(d));
+      if (d == kQsWindow) { d = kQsPaused; std::memcpy(at(si) + sizeof(uint64_t) * QS_DONE, &d, sizeof(d)); }
+    }
     ++si;
   }
   for (size_t i = 0; i < pk.size(); ++i) {
@@ -450,30 +495,63 @@ gg_status gg_coherent_snapshot_size(gg_ctx* ctx, uint64_t* bytes)
 {
   if (!ctx || !bytes) return gg_fail(GG_ERR_INVALID, "NULL argument");
   if (gg_status st = snap_valid(ctx, "gg_coherent_snapshot_size")) return st;
-  return coh_snapshot(ctx, nullptr, 0, bytes);
+  return coh_snapshot(ctx, nullptr, 0, bytes, false);
 }
 
 gg_status gg_coherent_snapshot(gg_ctx* ctx, void* host_buf, uint64_t cap, uint64_t* bytes)
 {
   if (!ctx || !bytes || !host_buf) return gg_fail(GG_ERR_INVALID, "NULL argument");
   if (gg_status st = snap_valid(ctx, "gg_coherent_snapshot")) return st;
-  return coh_snapshot(ctx, (uint8_t*)host_buf, cap, bytes);
+  return coh_snapshot(ctx, (uint8_t*)host_buf, cap, bytes, false);
 }
 
-gg_status gg_coherent_restore(gg_ctx* ctx, const gg_trace* tr, uint64_t* access_out_dev, const void* host_buf,
-                              uint64_t bytes, void* stream)
+gg_status gg_coherent_window_snapshot_size(gg_ctx* ctx, uint64_t* bytes)
 {
-  GG_NOT_ATAC(ctx, "gg_coherent_restore");
-  if (!ctx || !tr || !tr->tile_offsets || !host_buf) return gg_fail(GG_ERR_INVALID, "NULL argument");
-  if (gg_status st = coh_owns_all(ctx, GG_ERR_UNSUPPORTED, "gg_coherent_restore")) return st;
+  if (!ctx || !bytes) return gg_fail(GG_ERR_INVALID, "NULL argument");
+  if (gg_status st = snap_valid_win(ctx, "gg_coherent_window_snapshot_size")) return st;
+  return coh_snapshot(ctx, nullptr, 0, bytes, true);
+}
+
+gg_status gg_coherent_window_snapshot(gg_ctx* ctx, void* host_buf, uint64_t cap, uint64_t* bytes)
+{
+  if (!ctx || !bytes || !host_buf) return gg_fail(GG_ERR_INVALID, "NULL argument");
+  if (gg_status st = snap_valid_win(ctx, "gg_coherent_window_snapshot")) return st;
+  return coh_snapshot(ctx, (uint8_t*)host_buf, cap, bytes, true);
+}
+
+gg_status gg_window_snapshot_state(const void* host_buf, uint64_t bytes, uint32_t num_tiles, uint64_t* consumed,
+                                   uint8_t* finished)
+{
+  if (const char* why = ggsnap::win_read(host_buf, bytes, num_tiles, consumed, finished))
+    return gg_fail(GG_ERR_INVALID, "gg_window_snapshot_state: %s", why);
+  return GG_OK;
+}
+
+// windowed: gg_coherent_window_restore — tr is the tiles' first windows (tile
+// t's range begins at record consumed[t] of its trace), final_tiles as in
+// gg_coherent_begin_window; otherwise gg_coherent_restore over the whole trace
+static gg_status coh_restore(gg_ctx* ctx, const char* const what, bool windowed, const gg_trace* tr, uint64_t* access_out_dev,
+                             const uint8_t* final_tiles, const void* host_buf, uint64_t bytes, void* stream)
+{
+  GG_NOT_ATAC(ctx, what);
+  if (!ctx || !tr || !tr->tile_offsets || !host_buf) return gg_fail(GG_ERR_INVALID, "%s: NULL argument", what);
+  if (gg_status st = coh_owns_all(ctx, GG_ERR_UNSUPPORTED, what)) return st;
   hipSetDevice(ctx->device);
   if (gg_status st = coh_alloc(ctx)) return st;
   gg_coh_state* C = ctx->coh;
   const CP& P = C->P;
+  if (windowed && P.lat_l1d == 0)
+    return gg_fail(GG_ERR_UNSUPPORTED, "%s: with zero L1-D data cycles a record can cost no time, so no window "
+                                       "bounds what a tile consumes in a quantum", what);
   // ---- everything is checked before anything is changed ----
   ggsnap::View v;
-  if (const char* why = ggsnap::parse(host_buf, bytes, &v)) return gg_fail(GG_ERR_INVALID, "gg_coherent_restore: %s", why);
-  auto bad = [](const char* what) { return gg_fail(GG_ERR_INVALID, "gg_coherent_restore: %s", what); };
+  if (const char* why = ggsnap::parse(host_buf, bytes, &v)) return gg_fail(GG_ERR_INVALID, "%s: %s", what, why);
+  auto bad = [what](const char* why) { return gg_fail(GG_ERR_INVALID, "%s: %s", what, why); };
+  const uint8_t* wrecs = nullptr;
+  if (!windowed && v.find(ggsnap::kWinSection))
+    return bad("the snapshot is of a run fed in windows: gg_coherent_window_restore takes it");
+  if (windowed)
+    if (const char* why = ggsnap::win_section(v, P.T, &wrecs)) return bad(why);
   auto dense = [&](const char* name, uint64_t want) -> const ggsnap::Section* {
     const ggsnap::Section* x = v.find(name);
     return x && x->kind == ggsnap::SK_DENSE && x->bytes == want ? x : nullptr;
@@ -484,7 +562,8 @@ gg_status gg_coherent_restore(gg_ctx* ctx, const gg_trace* tr, uint64_t* access_
   const SnapLaunch sl = snap_launch(C);
   if (!(x = dense("launch", sizeof(SnapLaunch))) || std::memcmp(v.data(*x), &sl, sizeof(sl)))
     return bad("the snapshot was taken under a different derived launch state (environment knobs, build)");
-  if (!(x = dense("offsets", sizeof(uint64_t) * (P.T + 1))) || std::memcmp(v.data(*x), tr->tile_offsets, x->bytes))
+  if (!(x = dense("offsets", sizeof(uint64_t) * (P.T + 1))) ||
+      (!windowed && std::memcmp(v.data(*x), tr->tile_offsets, x->bytes)))
     return bad("the trace's tile_offsets are not the snapshot's");
   const ggsnap::Section* xst = v.find("stats");
   if (!xst || xst->kind != ggsnap::SK_DENSE || (xst->bytes & 7)) return bad("statistics-trace section");
@@ -499,7 +578,7 @@ gg_status gg_coherent_restore(gg_ctx* ctx, const gg_trace* tr, uint64_t* access_
   if (!xerr || !xctr || !xq || !xnd) return bad("a NoC or error-word section is missing or its size disagrees with the context");
   for (const gg_coh_state::Arr& a : C->arrs)
     if (snap_policy(a.name) == SN_DENSE && !dense(a.name, a.bytes))
-      return gg_fail(GG_ERR_INVALID, "gg_coherent_restore: section %s is missing or its size disagrees with the context", a.name);
+      return gg_fail(GG_ERR_INVALID, "%s: section %s is missing or its size disagrees with the context", what, a.name);
   // the prefix sections against the counts the snapshot itself carries
   SnapCounts n;
   n.nxl.resize(std::max(P.nsx, 1u)); n.nyl.resize(std::max(P.nsy, 1u));
@@ -517,20 +596,28 @@ gg_status gg_coherent_restore(gg_ctx* ctx, const gg_trace* tr, uint64_t* access_
     x = v.find(p.name);
     const uint64_t slots = (uint64_t)p.src.L * p.src.n;
     if (!x || x->kind != ggsnap::SK_PACKED || x->rec_bytes != p.src.rw * 8 || x->records > slots)
-      return gg_fail(GG_ERR_INVALID, "gg_coherent_restore: packed section %s is missing or does not fit the context", p.name);
+      return gg_fail(GG_ERR_INVALID, "%s: packed section %s is missing or does not fit the context", what, p.name);
     const uint8_t* r = v.data(*x);
     uint64_t prev = 0;
     for (uint64_t i = 0; i < x->records; ++i, r += x->rec_bytes) {   // slot indices: inside the arrays, ascending
       uint64_t g;
       std::memcpy(&g, r, 8);
       if (g >= slots || (i && g <= prev))
-        return gg_fail(GG_ERR_INVALID, "gg_coherent_restore: packed section %s, record %llu: slot index", p.name, (unsigned long long)i);
+        return gg_fail(GG_ERR_INVALID, "%s: packed section %s, record %llu: slot index", what, p.name, (unsigned long long)i);
       prev = g;
     }
+  }
+  if (windowed) {
+    // the windows against the records the tiles stood on (a device pass that reads no run state)
+    if (gg_status st = coh_trace_check(tr, P.T, what)) return st;
+    if (gg_status st = coh_window_restore_check(ctx, what, tr, final_tiles, wrecs, (hipStream_t)stream)) return st;
   }
   // ---- the usual reset, then the state ----
   if (gg_status st = gg_stats_restore_configure(ctx, stw.data())) return st;
   if (gg_status st = gg_coherent_begin(ctx, tr, access_out_dev, stream)) return st;
+  // (from here a failure of a windowed restore leaves no begun run, as in gg_coherent_begin_window)
+  struct Unbegin { gg_coh_state* C; bool on; ~Unbegin() { if (on) { C->begun = false; C->windowed = false; C->S.win = nullptr; } } }
+      unbegin{C, windowed};
   hipStream_t s = ctx->last_stream;
   const CS& S = C->S;
   if (gg_status st = gg_stats_restore_upload(ctx, stw.data(), stw.size(), s)) return st;
@@ -564,5 +651,21 @@ gg_status gg_coherent_restore(gg_ctx* ctx, const gg_trace* tr, uint64_t* access_
   }
   GG_HIP(hipStreamSynchronize(s));
   C->drv = gg_coh_state::DRV_DEVICE;                  // a snapshot is of the device loop's state
+  if (windowed) {
+    if (gg_status st = coh_window_restore_install(ctx, tr, s)) return st;
+    unbegin.on = false;
+  }
   return GG_OK;
+}
+
+gg_status gg_coherent_restore(gg_ctx* ctx, const gg_trace* tr, uint64_t* access_out_dev, const void* host_buf,
+                              uint64_t bytes, void* stream)
+{
+  return coh_restore(ctx, "gg_coherent_restore", false, tr, access_out_dev, nullptr, host_buf, bytes, stream);
+}
+
+gg_status gg_coherent_window_restore(gg_ctx* ctx, const gg_trace* win, uint64_t* access_out_dev, const uint8_t* final_tiles,
+                                     const void* host_buf, uint64_t bytes, void* stream)
+{
+  return coh_restore(ctx, "gg_coherent_window_restore", true, win, access_out_dev, final_tiles, host_buf, bytes, stream);
 }

@@ -43,6 +43,14 @@
 //       the run without --window prints.  A demonstration of the calls, not a
 //       fast path: the windows start at another record in every tile, so each
 //       hand-over is one generator launch per tile
+//   gg_replay --coherent ... --window RECORDS --checkpoint FILE --checkpoint-quantum Q
+//   gg_replay --coherent ... --window RECORDS --restore FILE
+//       the windowed run in legs (gg_coherent_window_snapshot / _window_restore):
+//       FILE holds the snapshot and the access words of the consumed records;
+//       the restored leg reads where every tile stands from FILE
+//       (gg_window_snapshot_state) and generates its windows from there, with
+//       any RECORDS.  A windowed checkpoint is restored with --window, an
+//       ordinary one without
 //   gg_replay --stats-trace-selftest
 //       prints both files' text for a fixed three-sample input (no GPU needed)
 //   gg_replay --format-table FILE...
@@ -357,8 +365,8 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "gg_replay: --checkpoint / --restore are for a single-process run\n");
         return 2;
       }
-      if (window && (!id_file.empty() || !ckpt_out.empty() || !ckpt_in.empty())) {
-        std::fprintf(stderr, "gg_replay: --window is for a single-process run without --checkpoint / --restore\n");
+      if (window && !id_file.empty()) {
+        std::fprintf(stderr, "gg_replay: --window is for a single-process run\n");
         return 2;
       }
       if (!id_file.empty()) {
@@ -415,6 +423,21 @@ int main(int argc, char** argv)
         DeviceBuffer<uint32_t> wm[2];
         DeviceBuffer<uint64_t> ww[2];                     // the windows' access words (bound, not printed)
         uint64_t handovers = 0;
+        // in legs (--checkpoint / --restore): the words of the consumed
+        // records are kept per tile and travel beside the snapshot; a restored
+        // leg takes where every tile stands from the file alone
+        const bool legs = !ckpt_out.empty() || !ckpt_in.empty();
+        const uint64_t stop = ckpt_out.empty() ? ~0ull : ckpt_quantum;
+        std::vector<std::vector<uint64_t>> words(tiles);
+        std::vector<uint8_t> blob;
+        if (!ckpt_in.empty()) {
+          readWindowCheckpoint(ckpt_in, tiles, blob, consumed, fin, words);
+          for (uint32_t t = 0; t < tiles; ++t)
+            if (consumed[t] > per_tile || (fin[t] != 0) != (consumed[t] == per_tile))
+              throw Error(GG_ERR_INVALID, ckpt_in + ": not a checkpoint of this trace (records per tile)");
+        }
+        uint64_t nq = 0;
+        int done = 0;
         for (int cur = 0;; cur ^= 1, ++handovers) {
           for (uint32_t t = 0; t < tiles; ++t) {
             const uint64_t left = per_tile - consumed[t];
@@ -429,15 +452,29 @@ int main(int argc, char** argv)
               check(gg_gen_hotspot_trace(wa[cur].p + woffs[t], wm[cur].p + woffs[t], t, 1, woffs[t + 1] - woffs[t],
                                          consumed[t], lines_log2, 26, hot_lines, 51, nullptr), "gg_gen_hotspot_trace");
           gg_trace w{wa[cur].p, wm[cur].p, woffs.data(), wn};
-          if (handovers == 0) check(gg_coherent_begin_window(be.ctx(), &w, ww[cur].p, fin.data(), nullptr), "gg_coherent_begin_window");
+          if (handovers == 0 && !ckpt_in.empty())
+            check(gg_coherent_window_restore(be.ctx(), &w, ww[cur].p, fin.data(), blob.data(), blob.size(), nullptr),
+                  "gg_coherent_window_restore");
+          else if (handovers == 0) check(gg_coherent_begin_window(be.ctx(), &w, ww[cur].p, fin.data(), nullptr), "gg_coherent_begin_window");
           else check(gg_coherent_next_window(be.ctx(), &w, ww[cur].p, fin.data(), nullptr), "gg_coherent_next_window");
-          uint64_t nq = 0;
-          int done = 0;
-          check(gg_coherent_advance(be.ctx(), ~0ull, &nq, &done), "gg_coherent_advance");
-          if (done == 1) break;
+          check(gg_coherent_advance(be.ctx(), stop, &nq, &done), "gg_coherent_advance");
+          if (done == 1 && !legs) break;
+          const std::vector<uint64_t> before(consumed);
           check(gg_coherent_window_state(be.ctx(), consumed.data(), need.data()), "gg_coherent_window_state");
+          for (uint32_t t = 0; legs && t < tiles; ++t) {
+            const uint64_t k = consumed[t] - before[t];
+            words[t].resize(consumed[t]);
+            if (k) hip_check(hipMemcpy(words[t].data() + before[t], ww[cur].p + woffs[t], 8 * k, hipMemcpyDeviceToHost), "copy access words");
+          }
+          if (done != GG_ADV_NEED_WINDOW) break;          // over, or paused at --checkpoint-quantum
         }
         std::fprintf(stderr, "gg_replay: %llu windows handed over\n", (unsigned long long)handovers);
+        if (!ckpt_out.empty()) {
+          writeWindowCheckpoint(ckpt_out, be, words);
+          std::fprintf(stderr, "gg_replay: %s at quantum %llu -> %s\n", done == 1 ? "run over" : "paused",
+                       (unsigned long long)nq, ckpt_out.c_str());
+          return 0;
+        }
       }
       else if (!ckpt_out.empty() || !ckpt_in.empty()) {
         // a run in legs: the access words travel with the snapshot

@@ -728,6 +728,54 @@ inline void readCheckpoint(const std::string& path, Backend& be, const gg_trace&
   if (words) hip_check(hipMemcpy(access_dev, w.data(), 8 * words, hipMemcpyHostToDevice), "copy access words");
   check(gg_coherent_restore(be.ctx(), &tr, access_dev, blob.data(), blob.size(), nullptr), "gg_coherent_restore");
 }
+// The same file for a run fed in windows (gg_coherent_window_snapshot): the
+// words are those of the consumed records, tile after tile (words[t] holds
+// tile t's, one per record it has consumed since begin).
+inline void writeWindowCheckpoint(const std::string& path, Backend& be, const std::vector<std::vector<uint64_t>>& words)
+{
+  uint64_t need = 0, total = 0;
+  check(gg_coherent_window_snapshot_size(be.ctx(), &need), "gg_coherent_window_snapshot_size");
+  std::vector<uint8_t> blob(need);
+  check(gg_coherent_window_snapshot(be.ctx(), blob.data(), need, &need), "gg_coherent_window_snapshot");
+  for (const std::vector<uint64_t>& w : words) total += w.size();
+  std::ofstream f(path, std::ios::binary);
+  const uint64_t hdr[2] = {need, total};
+  f.write(reinterpret_cast<const char*>(hdr), sizeof(hdr));
+  f.write(reinterpret_cast<const char*>(blob.data()), (std::streamsize)need);
+  for (const std::vector<uint64_t>& w : words) f.write(reinterpret_cast<const char*>(w.data()), (std::streamsize)(8 * w.size()));
+  f.close();
+  if (!f) throw Error(GG_ERR_INVALID, "cannot write " + path);
+}
+// the file back: the snapshot into blob (for gg_coherent_window_restore, which
+// takes the first windows too), where every tile stands (gg_window_snapshot_state)
+// and the consumed records' words
+inline void readWindowCheckpoint(const std::string& path, uint32_t tiles, std::vector<uint8_t>& blob,
+                                 std::vector<uint64_t>& consumed, std::vector<uint8_t>& finished,
+                                 std::vector<std::vector<uint64_t>>& words)
+{
+  std::ifstream f(path, std::ios::binary);
+  uint64_t hdr[2] = {0, 0};
+  if (!f || !f.read(reinterpret_cast<char*>(hdr), sizeof(hdr))) throw Error(GG_ERR_INVALID, "cannot read " + path);
+  f.seekg(0, std::ios::end);
+  const uint64_t size = (uint64_t)f.tellg();
+  if (hdr[0] > size || hdr[1] > size / 8 || size - hdr[0] != sizeof(hdr) + 8 * hdr[1])
+    throw Error(GG_ERR_INVALID, path + ": not a checkpoint (sizes)");
+  f.seekg(sizeof(hdr));
+  blob.resize(hdr[0]);
+  f.read(reinterpret_cast<char*>(blob.data()), (std::streamsize)hdr[0]);
+  if (!f) throw Error(GG_ERR_INVALID, "cannot read " + path);
+  consumed.assign(tiles, 0); finished.assign(tiles, 0);
+  check(gg_window_snapshot_state(blob.data(), blob.size(), tiles, consumed.data(), finished.data()), "gg_window_snapshot_state");
+  uint64_t total = 0;
+  for (uint64_t c : consumed) total += c;
+  if (total != hdr[1]) throw Error(GG_ERR_INVALID, path + ": the access words are not those of the consumed records");
+  words.assign(tiles, {});
+  for (uint32_t t = 0; t < tiles; ++t) {
+    words[t].resize(consumed[t]);
+    f.read(reinterpret_cast<char*>(words[t].data()), (std::streamsize)(8 * consumed[t]));
+  }
+  if (!f) throw Error(GG_ERR_INVALID, "cannot read " + path);
+}
 
 // Core::initiateMemoryAccess line split (core.cc:167-201): the line-aligned
 // addresses touched by [address, address + size), zero-size tail skipped.

@@ -752,17 +752,62 @@ gg_status gg_coherent_restore(gg_ctx* ctx, const gg_trace* trace, uint64_t* acce
  * The backstop: should a tile that is not final ever reach the end of its
  * window, the run ends with GG_ERR_STATE ("window exhausted"), never with
  * *done = 1 and never with a result.
- * On a windowed run gg_coherent_snapshot / _snapshot_size,
- * gg_coherent_advance_many, gg_coherent_run_many and gg_core_model_run (it
- * needs the whole trace) return GG_ERR_UNSUPPORTED; gg_coherent_quantum and
- * gg_round_* return GG_ERR_INVALID as for any advance-driven run.  A later
- * gg_coherent_begin, _run or _restore on the context starts an ordinary run. */
+ * On a windowed run gg_coherent_snapshot / _snapshot_size (their snapshot
+ * names positions in a resident trace: use gg_coherent_window_snapshot /
+ * _window_restore below), gg_coherent_advance_many, gg_coherent_run_many and
+ * gg_core_model_run (it needs the whole trace) return GG_ERR_UNSUPPORTED;
+ * gg_coherent_quantum and gg_round_* return GG_ERR_INVALID as for any
+ * advance-driven run.  A later gg_coherent_begin, _run or _restore on the
+ * context starts an ordinary run. */
 #define GG_ADV_NEED_WINDOW 3
 gg_status gg_coherent_begin_window(gg_ctx* ctx, const gg_trace* win, uint64_t* access_out_dev,
                                    const uint8_t* final_tiles, void* stream);
 gg_status gg_coherent_next_window(gg_ctx* ctx, const gg_trace* win, uint64_t* access_out_dev,
                                   const uint8_t* final_tiles, void* stream);
 gg_status gg_coherent_window_state(gg_ctx* ctx, uint64_t* consumed, uint64_t* min_records);
+/* A windowed run in legs: its snapshot and restore (DESIGN.md sections 4i, 4j).
+ *
+ * gg_coherent_window_snapshot / _size are gg_coherent_snapshot / _size for a
+ * run fed in windows, valid at its clean point: after
+ * gg_coherent_begin_window, after a gg_coherent_advance that returned *done 0,
+ * GG_ADV_NEED_WINDOW or 1, after gg_coherent_next_window, after
+ * gg_coherent_window_restore.  The container is the same with one more
+ * section, `win`: per tile the records consumed since begin, a finished flag
+ * and, for an unfinished tile, addr and meta of the record it stands on.
+ * Positions are stored as counts of consumed records, so the bytes do not
+ * depend on where the windows were cut: the final flags, the guards, the
+ * horizon and the bound arrays are not part of it.  The run is left exactly as
+ * it was.  GG_ERR_INVALID: a run that is not windowed (gg_coherent_snapshot
+ * takes it), a run that has failed (error word set, "window exhausted").
+ * GG_ERR_RANGE with *bytes = the need when cap is too small.
+ *
+ * gg_coherent_window_restore resets the context as gg_coherent_begin does,
+ * puts the state back (the statistics-trace configuration and the miss-type
+ * tables included) and installs win as gg_coherent_next_window would: tile
+ * t's range begins at record consumed[t] of its trace, final_tiles as in
+ * gg_coherent_begin_window, a blocked tile's pending record goes to the new
+ * access_out_dev.  Afterwards the run is windowed and driven by
+ * gg_coherent_advance; windows too short for the next quantum are no error
+ * (the next advance returns GG_ADV_NEED_WINDOW with no launch).
+ * GG_ERR_INVALID, with nothing changed and the context good for a fresh run:
+ * whatever gg_coherent_restore refuses (config, launch state, section sizes,
+ * a truncated or corrupted buffer), a snapshot without a `win` section
+ * (gg_coherent_restore takes it), a first record that differs in addr or meta
+ * from the stored one, an unfinished tile with an empty range, a finished
+ * tile with records, a tile that is not final with an empty window.
+ * GG_ERR_UNSUPPORTED as for gg_coherent_begin_window.  gg_coherent_restore
+ * given a snapshot with a `win` section returns GG_ERR_INVALID.
+ *
+ * gg_window_snapshot_state reads consumed[num_tiles] and finished[num_tiles]
+ * (host; either may be NULL) out of such a snapshot, with no context and no
+ * device: a fresh process cuts its first windows from the file alone.
+ * GG_ERR_INVALID with the parser's reason otherwise.                        */
+gg_status gg_coherent_window_snapshot_size(gg_ctx* ctx, uint64_t* bytes);
+gg_status gg_coherent_window_snapshot(gg_ctx* ctx, void* host_buf, uint64_t cap, uint64_t* bytes);
+gg_status gg_coherent_window_restore(gg_ctx* ctx, const gg_trace* win, uint64_t* access_out_dev,
+                                     const uint8_t* final_tiles, const void* host_buf, uint64_t bytes, void* stream);
+gg_status gg_window_snapshot_state(const void* host_buf, uint64_t bytes, uint32_t num_tiles, uint64_t* consumed,
+                                   uint8_t* finished);
 /* The coherent mode over ranks (one process per GPU), RCCL over xGMI.
  * nccl_comm is an ncclComm_t (RCCL) of W ranks; rank r's context must own
  * logical shards [r*K/W, (r+1)*K/W) (cfg.shard_begin / shard_end, K =
@@ -1351,7 +1396,7 @@ enum {
  * accesses unconsumed or run out of them, a register time of 2^62 ps or more
  * (the scoreboard keeps the unit in an entry's top two bits): the run's
  * error, reported by gg_iocoom_get_stats (GG_ERR_STATE).  GG_ERR_RANGE up
- * front for a tile of more than 2^31 instructions or accesses.
+ * front for a tile of more than 2^28 instructions or 2^31 accesses.
  * Asynchronous on stream.                                                    */
 gg_status gg_iocoom_run(gg_ctx* ctx, const gg_iocoom_params* params, const gg_ins* ins_dev,
                         const uint64_t* ins_tile_offsets, const uint64_t* acc_addr_dev, const uint32_t* acc_meta_dev,
